@@ -1,9 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- SpareNet loss/render hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: either that very command -- it re-launches itself as N ranks -- or
      python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does only what the headline needs: inputs, the untimed warm-up (which times the stream orders and keeps
+the fastest), exactly K timed steps, the result line.  --full adds everything else below -- the in-library launch
+timers and the sequential pass behind `roofline` / `segments_ms_rank0`, BASELINE's literal radii, the other scaling
+mode, other_ops, emd_regimes, network_steps and cpu_baseline -- each of which the --no-* options still turn off.
+--dump-outputs DIR writes what rank 0's last timed step computed as DIR/<name>.npy, float32 (dump_outputs): the
+losses, the per-point distances, assignments and input gradients of each part and a seeded sample of the depth
+maps, at most 64 MB in all.  The inputs are seeded, so two builds run with the same arguments can be compared
+file by file.
 
 One "step" = one pass of the hot path over one synthetic batch (BASELINE.json configs[1] + configs[2]):
     Chamfer distance            fwd + bwd   [B,16384,3] <-> [B,16384,3]
@@ -15,14 +24,14 @@ Scaling (whole clouds are independent, ranks own contiguous slices, n
     --scaling strong (default)  ONE global batch of 32 clouds (seed 1234) split with dist_utils.shard:
                                 32 / N clouds per rank -- SURVEY 8(e)'s split, the north star's >= 6x question
     --scaling weak              B = 32 clouds PER RANK, seed 1234 + rank (the same batch as strong at N = 1)
-  At N > 1 the other mode is timed after the headline region with the same K / W and reported in
+  At N > 1 with --full the other mode is timed after the headline region with the same K / W and reported in
   `other_scaling`, so one driver run per N yields both curves.
   `python bench.py --gpus N` with N > 1 and no launcher around it starts the N ranks itself (torch.distributed.run,
   one process per GPU, RCCL); under a launcher (WORLD_SIZE set) it is one of the ranks.
 The four parts are independent given the predicted cloud; by default the renderer runs on a second HIP
 stream next to the distance losses, and at <= 16 clouds per rank the expansion penalty on a third
 (config.streams = 2 / 3; --no-overlap times the one-stream step).
-After the timed region the same steps run once more one stream at a time, untimed for `value`, to
+With --full, after the timed region the same steps run once more one stream at a time, untimed for `value`, to
 report per-part times and the kernels' uncontended durations (roofline.isolated).
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line:
   value             point pairs per second, whole job (CD pairs 2*B*N*M + EMD effective pairs
@@ -30,14 +39,14 @@ Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line
   ms_per_step, step_ms_percentiles_rank0   wall / K, and median / p10 / p90 of the per-step durations (HIP
                     events on the main stream at the step boundaries)
   depthmaps_per_sec single-radius 256x256 maps per second over the same wall time
-  roofline          the dominant kernel (emd_auction_kernel, one launch per EMD call): `achieved` / `frac` =
+  roofline          (--full) the dominant kernel (emd_auction_kernel, one launch per EMD call): `achieved` / `frac` =
                     the work the kernel really ISSUED (matrix-core flops + vector lane operations from committed
                     PMC counters of the SAME build) / its launch time measured live with HIP events on the launch
                     stream, against the fp32 peak; `algorithmic_*` = SURVEY 8d's 14 flop x effective pairs over
                     the same time (the pruned search skips most algorithmic pairs, so that rate can exceed the
                     peak); `wait_frac`, `valu_busy`, `mfma_busy`, `traffic`; the same block for nn_search_kernel,
                     p2i_gather_max_kernel and (other_ops) mds_dense_team_kernel
-  cpu_baseline      the CPU oracle (port of the reference algorithm; the Chamfer single-thread leg is the
+  cpu_baseline      (--full) the CPU oracle (port of the reference algorithm; the Chamfer single-thread leg is the
                     reference's own CPU build when oracle/_ref is present) on a bounded sample, two legs
 """
 import argparse
@@ -83,6 +92,11 @@ def parse():
     ap.add_argument("--radius-list", type=str, default="5,7,10",
                     help="p2i radii in pixels (reference default, configs/base_config.py:56-60); "
                          "BASELINE.json's literal 0.02,0.05 is near-empty in pixel units")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, per-part times, literal radii, other scaling mode, other_ops, "
+                         "emd_regimes, network_steps, cpu_baseline (the --no-* options below pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what rank 0's last timed step computed as DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-overlap", action="store_true",
@@ -100,8 +114,14 @@ def parse():
     ap.add_argument("--no-other-scaling", action="store_true",
                     help="N > 1: skip the second timed region with the other scaling mode")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.scaling == "auto":
         args.scaling = "strong"
+    if not args.full:   # a plain run: the headline only
+        for k in ("no_cpu_baseline", "no_roofline", "no_network_steps", "no_emd_regimes", "no_other_ops",
+                  "no_literal_radii", "no_other_scaling"):
+            setattr(args, k, True)
     return args
 
 
@@ -170,6 +190,8 @@ class HotPath:
         self.three_streams_env = os.environ.get("BENCH_THREE_STREAMS")   # "0" / "1" force it (A/B); default: measured with the order
         # batch size -> (schedule name, {schedule: ms}) chosen by choose_schedule() during the untimed warm-up
         self.schedule = {}
+        # --dump-outputs: a dict while the last timed step runs; the parts keep references to what they computed
+        self.capture = None
 
     def _emd(self, pred, gt):
         """emdFunction with the effective-pair counter attached."""
@@ -198,14 +220,20 @@ class HotPath:
         p4 = (pred.detach() - 0.5).requires_grad_(True)
         if self.per_view:
             acc = None
+            views = []
             for v in range(N_VIEWS):
                 maps = self.render(p4, view_id=v, radius_list=self.radius_list)
+                if self.capture is not None:
+                    views.append(maps)
                 s = maps.mean()
                 acc = s if acc is None else acc + s
         else:
             maps = self.render.forward_views(p4, range(N_VIEWS), self.radius_list)       # [V,B,R,S,S]
+            views = [maps]
             acc = maps.mean() * N_VIEWS   # = the sum over the views of the mean map (one full reduction)
         acc.backward()
+        if self.capture is not None:
+            self.capture.update(depthmaps=views, render_grad=p4)
         return acc
 
     def step_overlapped(self, pred, gt):
@@ -349,10 +377,13 @@ class HotPath:
         # one wave per 512-point patch = lone waves for 0.35-0.45 ms, latency bound: next to another stream's work
         # it costs nothing, at the end of a chain it runs alone
         p3 = pred.detach().requires_grad_(True)
-        pen, _, mml = self.expansion(p3, PRIM, ALPHA)
+        pen, asg, mml = self.expansion(p3, PRIM, ALPHA)
         loss_exp = pen.mean()
         loss_exp.backward()
         self.last_mean_mst = mml.detach()
+        if self.capture is not None:
+            self.capture.update(expansion_dist=pen, expansion_assignment=asg, expansion_mean_mst_length=mml,
+                                expansion_grad=p3)
         return loss_exp
 
     def _loss_cd(self, pred, gt):
@@ -361,13 +392,17 @@ class HotPath:
         d1, d2 = self.cd(p, g)
         loss_cd = d1.mean() + d2.mean()
         loss_cd.backward()
+        if self.capture is not None:
+            self.capture.update(chamfer_dist1=d1, chamfer_dist2=d2, chamfer_grad1=p, chamfer_grad2=g)
         return loss_cd
 
     def _loss_emd(self, pred, gt):
         p2 = pred.detach().requires_grad_(True)
-        dist_, _ = self._emd(p2, gt)
+        dist_, asg = self._emd(p2, gt)
         loss_emd = torch.sqrt(dist_).mean(1).mean()
         loss_emd.backward()
+        if self.capture is not None:
+            self.capture.update(emd_dist=dist_, emd_assignment=asg, emd_grad=p2)
         return loss_emd
 
     def _distance_losses(self, pred, gt, mark=lambda name: None):
@@ -397,8 +432,10 @@ class HotPath:
         return losses
 
 
-def timed_region(hp, pred, gt, steps, warmup, overlap, barrier, before_timed=lambda: None, reduce_max=None):
-    """W untimed + exactly K timed steps between barrier + synchronize; returns (seconds, per-step ms, losses)."""
+def timed_region(hp, pred, gt, steps, warmup, overlap, barrier, before_timed=lambda: None, reduce_max=None,
+                 capture=False):
+    """W untimed + exactly K timed steps between barrier + synchronize; returns (seconds, per-step ms, losses).
+    capture: the last timed step leaves what it computed in hp.captured (dump_outputs)."""
     run_step = hp.step_overlapped if overlap else hp.step
     if overlap:   # untimed: which stream order is fastest on this batch (kept per batch size)
         hp.choose_schedule(pred, gt, reduce_max=reduce_max)
@@ -408,15 +445,20 @@ def timed_region(hp, pred, gt, steps, warmup, overlap, barrier, before_timed=lam
     hp.stats.zero_()
     before_timed()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+    last = steps - 1 if capture else -1
     barrier()
     t0 = time.perf_counter()
     marks[0].record()
     losses = None
     for k in range(steps):
+        if k == last:
+            hp.capture = {}
         losses = run_step(pred, gt)
         marks[k + 1].record()      # main stream: after the renderer's stream has been joined
     barrier()
     elapsed = time.perf_counter() - t0
+    if capture:
+        hp.captured, hp.capture = dict(hp.capture, losses=losses), None
     per_step = [marks[k].elapsed_time(marks[k + 1]) for k in range(steps)]
     return elapsed, per_step, losses
 
@@ -425,6 +467,48 @@ def percentiles(v):
     s = sorted(v)
     pick = lambda q: s[min(len(s) - 1, max(0, int(round(q * (len(s) - 1)))))]
     return {"median": pick(0.5), "p10": pick(0.1), "p90": pick(0.9), "min": s[0], "max": s[-1]}
+
+
+DUMP_MAP_PIXELS = 1 << 20        # depth-map values --dump-outputs keeps (the maps themselves: 8 x 32 x 3 x 256^2 floats)
+DUMP_MAP_SEED = 2024
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(captured, out_dir):
+    """--dump-outputs DIR: what the last timed step computed, one DIR/<name>.npy per array, float32 (assignment
+    indices are < 2^24: exact): the four losses the step returns, every part's per-point outputs, the gradients its
+    backward leaves on its inputs, and DUMP_MAP_PIXELS depth-map values at fixed seeded positions of the
+    [views, clouds, radii, 256, 256] maps.  Returns {name: shape}."""
+    import numpy as np
+
+    c = captured
+    arrays = {
+        "losses": c["losses"],
+        "chamfer_dist1": c["chamfer_dist1"], "chamfer_dist2": c["chamfer_dist2"],
+        "chamfer_grad_pred": c["chamfer_grad1"].grad, "chamfer_grad_gt": c["chamfer_grad2"].grad,
+        "emd_dist": c["emd_dist"], "emd_assignment": c["emd_assignment"], "emd_grad_pred": c["emd_grad"].grad,
+        "expansion_dist": c["expansion_dist"], "expansion_assignment": c["expansion_assignment"],
+        "expansion_mean_mst_length": c["expansion_mean_mst_length"],
+        "expansion_grad_pred": c["expansion_grad"].grad,
+        "render_grad_pred": c["render_grad"].grad,
+    }
+    maps = c["depthmaps"]
+    maps = (maps[0] if len(maps) == 1 else torch.stack(maps)).reshape(-1)   # per-view maps stack to the same layout
+    k = min(DUMP_MAP_PIXELS, maps.numel())
+    pick = np.sort(np.random.default_rng(DUMP_MAP_SEED).choice(maps.numel(), size=k, replace=False))
+    arrays["depthmaps_sample"] = maps[torch.from_numpy(pick).to(maps.device)]
+    out = {}
+    for name, t in arrays.items():
+        if t is None:
+            raise RuntimeError(f"--dump-outputs: the last timed step left no {name}")
+        out[name] = t.detach().to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def cpu_baseline():
@@ -848,10 +932,16 @@ def main():
             lib.sn_emd_prof_exec(None, 1)
             lib.sn_prof_enable(1)
 
-    elapsed, per_step, losses = timed_region(hp, pred, gt, args.steps, args.warmup, overlap, barrier, prof_on, reduce_max)
+    dump = args.dump_outputs is not None and rank == 0
+    elapsed, per_step, losses = timed_region(hp, pred, gt, args.steps, args.warmup, overlap, barrier, prof_on, reduce_max,
+                                             capture=dump)
     lib.sn_prof_enable(0)
     hp.lib.check(lib.sn_device_status(), "timed region")   # a team barrier that gave up inside it (NaN losses) is an error
     stats_timed = hp.stats.clone()
+    dumped = None
+    if dump:
+        dumped = dump_outputs(hp.captured, args.dump_outputs)
+        del hp.captured
 
     def read_kernels():
         ks = {}
@@ -1147,6 +1237,8 @@ def main():
             "kernels_isolated_rank0": kernels_isolated,
             "losses": [float(x) for x in losses.tolist()],
             "roofline": roofline,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
         if world == 1 and not args.no_other_ops:
             oo = other_ops(dev, pred, hp.last_mean_mst)

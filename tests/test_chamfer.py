@@ -41,19 +41,23 @@ def test_oracle_mt_equals_single_thread():
         assert np.array_equal(p, q)
 
 
-def test_oracle_vs_live_reference_build():
-    """When oracle/_ref/cd_ref.so exists (built from /root/reference), check live."""
+def test_oracle_vs_live_reference_build(golden_dir):
+    """The reference's own CPU build on two fixed clouds (seed 77) against the oracle: its output as stored by
+    tests/golden/gen_chamfer.py, and live as well where oracle/_ref/cd_ref.so is built."""
     from oracle import ref
 
-    if not ref.available():
-        pytest.skip("oracle/_ref not built here")
+    z = np.load(os.path.join(golden_dir, "refbuild_chamfer_2x513x1025.npz"))
     g = torch.Generator().manual_seed(77)
     x = torch.rand(2, 513, 3, generator=g)
     y = torch.rand(2, 1025, 3, generator=g)
-    d1, d2, i1, i2 = ref.chamfer_forward(x, y)
+    assert np.array_equal(x.numpy(), z["xyz1"]) and np.array_equal(y.numpy(), z["xyz2"])
+    want = [z[k] for k in ("dist1", "dist2", "idx1", "idx2")]
+    if ref.available():
+        for p, q in zip(want, ref.chamfer_forward(x, y)):
+            assert np.array_equal(p, q.numpy())
     o = oracle.chamfer_forward(x.numpy(), y.numpy())
-    for p, q in zip(o, (d1, d2, i1, i2)):
-        assert np.array_equal(p, q.numpy())
+    for p, q in zip(o, want):
+        assert np.array_equal(p, q)
 
 
 def test_host_path_matches_reference_golden_config1(golden_dir):

@@ -7,6 +7,6 @@ for v in "" "$@"; do
   AB_LIB=$v AB_BS=32,4 python tools/emd_ab.py 2>&1 | grep "per call"
   for order in "" auction_first; do
     echo -n "order=${order:-default}: "
-    AB_LIB=$v BENCH_ORDER=$order timeout 300 python bench.py --no-cpu-baseline --no-other-ops --no-network-steps --no-literal-radii --steps 30 --warmup 5 2>/dev/null | line
+    AB_LIB=$v BENCH_ORDER=$order timeout 300 python bench.py --full --no-cpu-baseline --no-other-ops --no-network-steps --no-literal-radii --steps 30 --warmup 5 2>/dev/null | line
   done
 done

@@ -9,7 +9,7 @@ echo "== PMC (four counter-only passes over tools/step_probe.py)"
 timeout 900 tools/pmc_all.sh profiles/r03_${TAG}_pmc_all_kernels.json > $O/pmc.log 2>&1; tail -3 $O/pmc.log | cut -c1-400
 cp profiles/r03_${TAG}_pmc_all_kernels.json $O/pmc_all_kernels.json
 echo "== bench (quotes the counters just taken: same build)"
-timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err | cut -c1-300
+timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err | cut -c1-300
 python - <<PY
 import json
 d = json.load(open("$O/bench.json"))
@@ -36,5 +36,5 @@ echo "== mds teams"; timeout 600 python tools/mds_ab.py 2>&1 | grep -v amdgpu | 
 echo "== render kernels"; (python tools/render_probe.py; KTOP=12 tools/kstats.sh tools/render_probe.py) 2>&1 | grep -v "amdgpu\|^E2026" | tee $O/render_kernels.txt | tail -12
 echo "== chamfer collapsed"; python tools/chamfer_collapsed.py 2>&1 | grep chamfer | tee $O/chamfer_collapsed.txt
 echo "== traffic calibration"; timeout 600 tools/traffic_calibration.sh $O/traffic_calibration.json | tee $O/traffic_calibration.txt
-echo "== launcher"; BENCH_DEBUG_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --no-roofline 2>/dev/null | grep '^{' > $O/bench_gpus2_shared_gpu.json; python -c "
+echo "== launcher"; BENCH_DEBUG_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --full --no-roofline 2>/dev/null | grep '^{' > $O/bench_gpus2_shared_gpu.json; python -c "
 import json; d=json.load(open('$O/bench_gpus2_shared_gpu.json')); print({k: d[k] for k in ('n_gpus','scaling','ms_per_step')}, d['rccl_ranks']['backend'], d['other_scaling']['scaling'], d['other_scaling']['ms_per_step'])"

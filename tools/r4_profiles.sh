@@ -10,7 +10,7 @@ echo "== PMC (four counter-only passes over tools/step_probe.py)"
 timeout 900 tools/pmc_all.sh profiles/r04_${TAG}_pmc_all_kernels.json > $O/pmc.log 2>&1; tail -3 $O/pmc.log | cut -c1-400
 cp profiles/r04_${TAG}_pmc_all_kernels.json $O/pmc_all_kernels.json
 echo "== bench (quotes the counters just taken: same build)"
-timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err | cut -c1-300
+timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err | cut -c1-300
 python - <<PY
 import json
 d = json.load(open("$O/bench.json"))
@@ -30,7 +30,7 @@ cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $
 f=$(find gpurun_out/kst -name "*kernel_stats.csv" | head -1); cp $f $O/kernel_stats.csv; head -8 $f | cut -c1-160; rm -rf gpurun_out/kst
 echo "== stream order A/B"
 line() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels_rank0']; ki=d['kernels_isolated_rank0']; print(round(d['ms_per_step'],3), 'ms per step; one stream', round(d['sequential_ms_per_step_rank0'],3), '; auction bracket / execution window / isolated us', round(k['emd_auction']['avg_us']), round(k['emd_auction_exec']['avg_us']), round(ki['emd_auction']['avg_us']), '; gather live / isolated us', round(k['p2i_max_splat']['avg_us']), round(ki['p2i_max_splat']['avg_us']))"; }
-BA="--no-cpu-baseline --no-other-ops --no-network-steps --no-literal-radii --steps 30 --warmup 8"
+BA="--full --no-cpu-baseline --no-other-ops --no-network-steps --no-literal-radii --steps 30 --warmup 8"
 for o in chain auction_first; do echo -n "BENCH_ORDER=$o: "; BENCH_ORDER=$o timeout 300 python bench.py $BA 2>/dev/null | line; done | tee $O/order_ab.txt
 echo "== emd phases + per batch size"
 SN_EMD_DIAG=2 AB_BS=32 AB_DIAG_B=32 timeout 600 python tools/emd_ab.py 2>&1 | grep -v amdgpu > $O/emd_phases_b32.txt; tail -2 $O/emd_phases_b32.txt | cut -c1-250
@@ -56,6 +56,6 @@ timeout 300 python tools/net_host_profile.py config5 trained_stand_in 2>&1 | gre
 echo "== graph replay"
 { for a in "emd" "emd null+autofree" "chamfer"; do echo "-- raw HIP graph: $a"; SN_ALLOW_CAPTURE=1 timeout 60 tools/probe/graph_emd $a; done
   echo "-- torch.cuda.CUDAGraph (tools/capture_probe.py)"; timeout 600 python tools/capture_probe.py 2>&1 | grep -v amdgpu; } > $O/graph_replay.txt 2>&1; grep -c "equal to eager: 1" $O/graph_replay.txt
-echo "== launcher"; BENCH_DEBUG_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --no-roofline 2>/dev/null | grep '^{' > $O/bench_gpus2_shared_gpu.json; python -c "
+echo "== launcher"; BENCH_DEBUG_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --full --no-roofline 2>/dev/null | grep '^{' > $O/bench_gpus2_shared_gpu.json; python -c "
 import json; d=json.load(open('$O/bench_gpus2_shared_gpu.json')); print({k: d[k] for k in ('n_gpus','scaling','ms_per_step')}, d['rccl_ranks']['backend'], d['other_scaling']['scaling'], d['other_scaling']['ms_per_step'])"
 echo done > $O/done.txt

@@ -10,7 +10,7 @@ echo "== PMC (four counter-only passes over tools/step_probe.py)"
 timeout 900 tools/pmc_all.sh profiles/r05_${TAG}_pmc_all_kernels.json > $O/pmc.log 2>&1; tail -3 $O/pmc.log | cut -c1-400
 cp profiles/r05_${TAG}_pmc_all_kernels.json $O/pmc_all_kernels.json
 echo "== bench (quotes the counters just taken: same build)"
-timeout 1800 python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err | cut -c1-300
+timeout 1800 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err | cut -c1-300
 python - <<PY
 import json
 d = json.load(open("$O/bench.json"))
@@ -52,6 +52,6 @@ for cfg in config4 config5; do
   done
 done
 cd $R
-echo "== launcher"; BENCH_DEBUG_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --no-roofline 2>/dev/null > $O/bench_gpus2.out; python -c "
+echo "== launcher"; BENCH_DEBUG_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --full --no-roofline 2>/dev/null > $O/bench_gpus2.out; python -c "
 import json; t=open('$O/bench_gpus2.out').read(); t=t[t.index('{\"metric\"'):]; d=json.loads(t[:t.rindex('}')+1]); json.dump(d, open('$O/bench_gpus2_shared_gpu.json','w')); print({k: d[k] for k in ('n_gpus','scaling','ms_per_step')}, d['rccl_ranks']['backend'], d['other_scaling']['scaling'], d['other_scaling']['ms_per_step'])"
 echo done > $O/done.txt
