@@ -49,6 +49,29 @@ const char *sn_last_error(void);
  * a time-out in the step that just finished instead of at the next sn_emd_* / sn_mds call. */
 int sn_device_status(void);
 
+/* Wait policy of the two ops whose workgroups wait for each other inside one launch (the persistent EMD auction's
+ * teams, the density sampler's teams).  On a device shared with another process a team can lose compute units to it
+ * and give up after its bounded spin:
+ *   SN_WAIT_FAIL    (default) the unfinished clouds come back as NaN / -1 rows and the device's sticky word makes the
+ *                   next sn_emd_* / sn_mds call (or sn_device_status) return SN_ETIMEDOUT;
+ *   SN_WAIT_RECOVER teams as by default, but a team that gives up leaves the sticky word alone: the same call
+ *                   recomputes its clouds on the same stream with kernels that wait for nobody (exact: the same
+ *                   results as a call that never timed out) and counts them.  Once a recovery has been seen on a
+ *                   device (the counters of sn_wait_report grew) later calls there take the non-waiting path
+ *                   directly (the "latch", cleared by sn_set_wait_policy);
+ *   SN_WAIT_NOWAIT  never launch a team-waiting kernel: the auction runs with teams of one workgroup, the sampler with
+ *                   its one-workgroup kernel.
+ * The policy is process-wide; SN_WAIT_POLICY=fail|recover|nowait in the environment gives its initial value.
+ * sn_set_wait_policy returns SN_EINVAL for any other value.  sn_wait_report writes the first min(n, 3) of: EMD clouds
+ * recovered on the current device, sampler clouds recovered there, 1 if the device's latch is set; like
+ * sn_device_status it reads pinned host words without a synchronisation (meaningful for work that has finished). */
+#define SN_WAIT_FAIL 0
+#define SN_WAIT_RECOVER 1
+#define SN_WAIT_NOWAIT 2
+int sn_set_wait_policy(int policy);
+int sn_wait_policy(void);
+int sn_wait_report(long long *out, int n);
+
 /* Optional per-kernel timing, off by default (measurement aid, not part of the
  * reference interface): when enabled the heavy kernels ("chamfer_fwd", "emd_auction",
  * "expansion_fwd", "mds", "p2i_max_splat" = the binned gather) are bracketed by hipEventRecord on the
@@ -120,20 +143,28 @@ int sn_chamfer_backward_host(const float *xyz1, const float *xyz2,
  * dist[b,n] fp32, assignment[b,n] int32.
  * All iterations run in ONE persistent launch (one workgroup per compute unit; teams of
  * workgroups own a cloud and synchronise through bounded, placement-independent barriers).
- * Environment: SN_EMD_CHECK=1 makes the call synchronise and fail if a barrier timed out.
+ * Environment: SN_EMD_CHECK=1 makes the call synchronise and fail if a barrier timed out (under SN_WAIT_RECOVER: if
+ * a time-out survived the recovery pass).
  * stats (optional device pointer, may be NULL): 2 x int64, zeroed by the caller
  *   stats[0] += sum over iterations and batch of unassigned_count * n
  *               (effective pair evaluations); stats[1] += iterations that had
  *               at least one bidder (one atomic per cloud per iteration).
+ *   In a call that recovered clouds (SN_WAIT_RECOVER) both also hold the iterations the abandoned team launch had
+ *   done before it gave up, on top of the recovery's complete run of those clouds.
  * With SN_EMD_DIAG=1|2 in the environment the call also leaves phase timers of the first team
  * in the workspace, 16 + 64*64 int64 words at sn_emd_diag_offset (tools/emd_ab.py).
  *
  * Failure behaviour (the reference returns an error code from emd_cuda_forward, emd_cuda.cu:276-281): the
  * auction is ONE persistent launch whose workgroups wait for each other; every wait is bounded (> 2 s).  If a
- * barrier gives up (a CU withheld from the launch by another tenant or a debugger), every workgroup leaves,
- * the unfinished clouds get dist = NaN and assignment = -1, and the NEXT sn_emd_forward / sn_emd_backward call
- * on that device returns SN_ETIMEDOUT without a host synchronisation (SN_EMD_CHECK=1: the failing call itself
- * synchronises and returns SN_EINVAL).
+ * barrier gives up (a CU withheld from the launch by another tenant or a debugger), every workgroup leaves and
+ * the unfinished clouds get dist = NaN and assignment = -1.  Then, by the wait policy (sn_set_wait_policy):
+ *   fail (default): the NEXT sn_emd_forward / sn_emd_backward call on that device returns SN_ETIMEDOUT without a
+ *     host synchronisation (SN_EMD_CHECK=1: the failing call itself synchronises and returns SN_EINVAL);
+ *   recover: a recovery pass enqueued behind the launch (no host synchronisation) picks the NaN / -1 clouds on the
+ *     device, redoes their set-up and runs their auction with teams of one workgroup; the result is bit-identical
+ *     to a call that never timed out, and sn_wait_report counts the clouds.  Without a time-out the pass costs one
+ *     small launch and three launches whose workgroups leave at once;
+ *   nowait: teams of one workgroup from the start (no workgroup waits for another).
  * Memory-model note: the launch hands data between workgroups with relaxed coherent accesses and no fences, and
  * keeps the stores of a team that sits on one XCD in that XCD's L2.  This is gfx950 behaviour, verified once per
  * device by a litmus kernel at the first call; on failure, or with SN_EMD_SAFE=1, the launch uses agent-scope
@@ -183,11 +214,15 @@ int sn_expansion_backward(const float *xyz, const float *graddist,
  * The `temp` tensor MDS.cpp:119-121 allocates lives in registers; only clouds
  * with more than 24576 points need `workspace` (sn_mds_workspace_bytes() > 0).
  * The density kernel is sn_expf (include/sn_expf.h), not libm/OCML expf.
- * Clouds of 2048 .. 20352 points are cluster-sorted and sampled either by one workgroup each or by a TEAM of up to
+ * Clouds of 2048 .. 19456 points are cluster-sorted and sampled either by one workgroup each or by a TEAM of up to
  * 32 workgroups per cloud that takes several exact picks per exchange (every cloud of >= 8192 points when teams of
  * >= 8 fit the device; index sequences are the reference's either way).  A team's bounded waits can give up when the
- * device is shared with something that keeps compute units from the launch: the row is then -1 and the next sn_mds /
- * sn_emd_* call -- or sn_device_status() -- reports SN_ETIMEDOUT. */
+ * device is shared with something that keeps compute units from the launch; the cloud's row is then -1, and by the
+ * wait policy (sn_set_wait_policy):
+ *   fail (default): the next sn_mds / sn_emd_* call -- or sn_device_status() -- reports SN_ETIMEDOUT;
+ *   recover: the one-workgroup kernel, which runs behind the team kernel on the same stream anyway, also samples
+ *     every team cloud whose row starts with -1 (index-exact, counted in sn_wait_report);
+ *   nowait: no teams, every cloud on one workgroup (as under graph capture). */
 size_t sn_mds_workspace_bytes(int b, int n);
 int sn_mds(const float *xyz, int b, int n, int m, const float *mean_mst_length,
            int *idx, void *workspace, size_t workspace_bytes, void *stream);

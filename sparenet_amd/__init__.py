@@ -14,11 +14,49 @@ _REFERENCE_OP_PACKAGES = ("chamfer_distance", "chamfer_dist", "emd", "expansion_
                           "gridding", "gridding_loss", "cubic_feature_sampling")
 
 
+WAIT_POLICIES = ("fail", "recover", "nowait")   # SN_WAIT_FAIL / SN_WAIT_RECOVER / SN_WAIT_NOWAIT (sparenet_hip.h)
+
+
+def set_wait_policy(name):
+    """What the ops whose workgroups wait for each other (the EMD auction's teams, the density sampler's teams) do on a
+    GPU shared with another process: "fail" (default: a team that gives up leaves NaN / -1 rows and the next op, or
+    `loss_item`, raises), "recover" (the same call recomputes those clouds with kernels that wait for nobody -- exact
+    -- and later calls on that device skip the teams) or "nowait" (never launch a team).  Process-wide; the
+    environment variable SN_WAIT_POLICY gives the initial value.  Setting a policy clears the per-device latch of
+    "recover"."""
+    if name not in WAIT_POLICIES:
+        raise ValueError(f"unknown wait policy {name!r}: expected one of {', '.join(WAIT_POLICIES)}")
+    from ._lib import check
+
+    check(lib().sn_set_wait_policy(WAIT_POLICIES.index(name)), "sn_set_wait_policy")
+
+
+def wait_policy():
+    """The current wait policy's name (see set_wait_policy)."""
+    return WAIT_POLICIES[lib().sn_wait_policy()]
+
+
+def wait_report():
+    """Recoveries on the CURRENT device since the process started: {"emd_recovered": clouds, "mds_recovered": clouds,
+    "latched": whether later calls there skip the teams}.  Reads pinned host words without a synchronisation: it
+    covers work that has finished (call it after a `.item()` / synchronize)."""
+    import ctypes
+
+    from ._lib import check
+
+    out = (ctypes.c_longlong * 3)()
+    check(lib().sn_wait_report(out, 3), "sn_wait_report")
+    return {"emd_recovered": int(out[0]), "mds_recovered": int(out[1]), "latched": bool(out[2])}
+
+
 def loss_item(loss):
     """`loss.item()` that cannot hand back the number of a failed step: the host waits for the GPU (as `.item()` always
     does), then the device's sticky error word is read (sn_device_status) -- if a team barrier of the persistent EMD
     auction or of the density sampler timed out in any launch up to here (a shared device, a debugger holding a compute
     unit), its outputs were NaN / -1 and this raises SparenetHipError instead of returning NaN to the training loop.
+    That is the default wait policy ("fail"); under `set_wait_policy("recover")` the call that met the time-out has
+    already recomputed those clouds exactly, nothing is raised and the loss is the one an undisturbed step computes
+    (`wait_report()` counts the recoveries); under "nowait" no op waits for another workgroup in the first place.
     Where the reference's runners log `_loss.item()` every step (runners/sparenet_runner.py:113-116), log
     `sparenet_amd.loss_item(_loss)` -- before `optimizer.step()` if a failed step must not touch the weights."""
     value = loss.item()

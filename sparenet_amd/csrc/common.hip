@@ -2,6 +2,7 @@
 #include "common.hpp"
 
 #include <atomic>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -57,9 +58,14 @@ void prof_end(const char *name, hipStream_t s) {
 }
 
 namespace {
+// One pinned page per device: word 0 = the sticky error word, words 1 + kRecoveredEmd / 1 + kRecoveredMds = clouds
+// recovered under SN_WAIT_RECOVER (only ever grow).  seen[] = the counters at the last look, latched = a recovery
+// was seen since the last sn_set_wait_policy (see wait_solo).
 struct Sticky {
   unsigned *host = nullptr, *dev = nullptr;
   bool tried = false;
+  unsigned seen[2] = {0u, 0u};
+  bool latched = false;
 };
 std::mutex g_sticky_mu;
 Sticky g_sticky[64];
@@ -73,7 +79,7 @@ unsigned *sticky_device_word(int dev) {
     st.tried = true;
     void *h = nullptr;
     if (hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess) {
-      *static_cast<volatile unsigned *>(h) = 0u;
+      for (int i = 0; i < 3; ++i) static_cast<volatile unsigned *>(h)[i] = 0u;
       void *d = nullptr;
       if (hipHostGetDevicePointer(&d, h, 0) == hipSuccess && d) {
         st.host = static_cast<unsigned *>(h);
@@ -139,6 +145,52 @@ void clear_sticky(int dev) {
   if (g_sticky[dev].host) *reinterpret_cast<volatile unsigned *>(g_sticky[dev].host) = 0u;
 }
 
+unsigned *recovered_device_word(int dev, int which) {
+  unsigned *w = sticky_device_word(dev);
+  return w ? w + 1 + which : nullptr;
+}
+
+namespace {
+std::atomic<int> g_wait_policy{-1};  // -1: not read yet (SN_WAIT_POLICY gives the initial value)
+
+int parse_wait_policy(const char *e) {
+  if (!e || !strcmp(e, "fail") || !strcmp(e, "0")) return SN_WAIT_FAIL;
+  if (!strcmp(e, "recover") || !strcmp(e, "1")) return SN_WAIT_RECOVER;
+  if (!strcmp(e, "nowait") || !strcmp(e, "2")) return SN_WAIT_NOWAIT;
+  fprintf(stderr, "sparenet_hip: SN_WAIT_POLICY=%s is not fail / recover / nowait; using fail\n", e);
+  return SN_WAIT_FAIL;
+}
+
+// reads the two counters of `st` (caller holds g_sticky_mu); sets the latch if either grew since the last look
+void refresh_latch(Sticky &st) {
+  if (!st.host) return;
+  for (int i = 0; i < 2; ++i) {
+    const unsigned v = reinterpret_cast<volatile unsigned *>(st.host)[1 + i];
+    if (v != st.seen[i]) st.latched = true;
+    st.seen[i] = v;
+  }
+}
+}  // namespace
+
+int wait_policy() {
+  int p = g_wait_policy.load(std::memory_order_relaxed);
+  if (p < 0) {
+    int want = -1;
+    g_wait_policy.compare_exchange_strong(want, parse_wait_policy(SN_KNOB("SN_WAIT_POLICY")));
+    p = g_wait_policy.load(std::memory_order_relaxed);
+  }
+  return p;
+}
+
+bool wait_solo(int dev) {
+  const int p = wait_policy();
+  if (p == SN_WAIT_NOWAIT) return true;
+  if (p != SN_WAIT_RECOVER || dev < 0 || dev >= 64) return false;
+  std::lock_guard<std::mutex> lk(g_sticky_mu);
+  refresh_latch(g_sticky[dev]);
+  return g_sticky[dev].latched;
+}
+
 }  // namespace sn
 
 extern "C" void sn_prof_enable(int on) { sn::g_prof.store(on != 0); }
@@ -187,6 +239,37 @@ extern "C" int sn_device_status(void) {
     return 0;
   }
   return sn::check_sticky(dev, "sn_device_status");
+}
+
+// Wait policy of the team-waiting launches (sparenet_hip.h).  Process-wide; setting it clears every device's latch.
+extern "C" int sn_set_wait_policy(int policy) {
+  SN_REQUIRE(policy == SN_WAIT_FAIL || policy == SN_WAIT_RECOVER || policy == SN_WAIT_NOWAIT,
+             "sn_set_wait_policy: policy must be 0 (fail), 1 (recover) or 2 (nowait), got %d", policy);
+  std::lock_guard<std::mutex> lk(sn::g_sticky_mu);
+  sn::g_wait_policy.store(policy, std::memory_order_relaxed);
+  for (auto &st : sn::g_sticky) {
+    sn::refresh_latch(st);
+    st.latched = false;
+  }
+  return 0;
+}
+
+extern "C" int sn_wait_policy(void) { return sn::wait_policy(); }
+
+// out[0] = EMD clouds recovered on the current device, out[1] = sampler clouds recovered, out[2] = 1 if the latch is
+// set (the first min(n, 3) of them are written).  Pinned host words, no synchronisation: meaningful for finished work.
+extern "C" int sn_wait_report(long long *out, int n) {
+  SN_REQUIRE(out && n >= 1, "sn_wait_report: need an output array of n >= 1 values");
+  int dev = 0;
+  SN_HIP(hipGetDevice(&dev));
+  SN_REQUIRE(dev >= 0 && dev < 64, "sn_wait_report: unexpected device ordinal %d", dev);
+  (void)sn::sticky_device_word(dev);
+  std::lock_guard<std::mutex> lk(sn::g_sticky_mu);
+  sn::Sticky &st = sn::g_sticky[dev];
+  sn::refresh_latch(st);
+  const long long v[3] = {(long long)st.seen[0], (long long)st.seen[1], st.latched ? 1ll : 0ll};
+  for (int i = 0; i < n && i < 3; ++i) out[i] = v[i];
+  return 0;
 }
 
 extern "C" int sn_abi_version(void) { return SN_ABI_VERSION; }

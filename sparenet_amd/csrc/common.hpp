@@ -53,10 +53,22 @@ void prof_end(const char *name, hipStream_t s);
 
 // Per-device sticky error word (pinned host memory, device-visible): a kernel whose workgroups wait for each other
 // (the persistent EMD auction, the multi-workgroup density sampler) sets it when a bounded wait gives up; the next
-// call of such an op on the device returns SN_ETIMEDOUT without a host synchronisation.
+// call of such an op on the device returns SN_ETIMEDOUT without a host synchronisation.  Under SN_WAIT_RECOVER the
+// kernels do not set it: the call recomputes what the team left unfinished (sn_emd_forward, sn_mds).
 unsigned *sticky_device_word(int dev);            // nullptr if the word could not be allocated
 int check_sticky(int dev, const char *what);      // 0, or SN_ETIMEDOUT (clears the word, fills sn_last_error)
 void clear_sticky(int dev);
+
+// Wait policy (sn_set_wait_policy, SN_WAIT_POLICY): SN_WAIT_FAIL / SN_WAIT_RECOVER / SN_WAIT_NOWAIT.
+int wait_policy();
+// Counters of clouds a recovery pass recomputed, next to the sticky word in the same pinned page (device pointers,
+// bumped with system-scope atomics; nullptr if the page could not be allocated): kRecoveredEmd / kRecoveredMds.
+constexpr int kRecoveredEmd = 0, kRecoveredMds = 1;
+unsigned *recovered_device_word(int dev, int which);
+// true when calls on `dev` must not launch a team-waiting kernel: policy SN_WAIT_NOWAIT, or SN_WAIT_RECOVER after a
+// recovery has been seen on the device (a counter grew since the last look: the latch is set then and stays set until
+// the next sn_set_wait_policy).  Reads the pinned counters, no synchronisation.
+bool wait_solo(int dev);
 
 // Launches whose workgroups WAIT for each other (the persistent EMD auction, the sampler's dense-regime teams) must
 // not overlap each other on a device: each may hold compute units with members of a not-yet-complete team, and two

@@ -61,6 +61,9 @@ constexpr int kThreads = 256;     // element-wise kernels
 #define SN_EMD_WAVES 4
 #endif
 constexpr int kRankBins = 256;    // per cloud: counters of unassigned bidders per 1/256 of the Hilbert ranks
+// Recovery mask of SN_WAIT_RECOVER (emd_recover_mark_kernel): one word per cloud (b <= 512) + the number of marked
+// clouds at kRecAny, in the last kRecWords words of the control block (see sn_emd_forward for the bound)
+constexpr int kRecAny = 512, kRecWords = 544;
 
 
 struct Top2 {
@@ -285,12 +288,21 @@ struct EmdWs {
   void *ctl;     // persistent auction: ticket, abort word, one barrier counter per team
 };
 
+// rmask (recovery pass of SN_WAIT_RECOVER, see emd_recover_mark_kernel; nullptr = every cloud): only the clouds it
+// marks are set up again, and with none marked every workgroup leaves at once.  The same for emd_seed_kernel.
 __global__ void emd_init_kernel(int B, int n, const float *__restrict__ xyz2,
-                                int *__restrict__ assignment, EmdWs ws) {
+                                int *__restrict__ assignment, EmdWs ws, const unsigned *__restrict__ rmask = nullptr) {
 #pragma clang fp contract(off)
+  if (rmask && rmask[kRecAny] == 0u) return;
   const long total = (long)B * n;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (long)gridDim.x * blockDim.x) {
+    if (e < (long)B * kRankBins && (!rmask || rmask[e / kRankBins])) {
+      ws.bins[0][e] = n / kRankBins;  // every bidder starts unassigned
+      ws.bins[1][e] = 0;
+    }
+    if (e < B && (!rmask || rmask[e])) ws.far[e] = 0;
+    if (rmask && !rmask[e / n]) continue;
     assignment[e] = -1;
     ws.assignment_inv[e] = -1;
     ws.price[e] = 0.f;
@@ -320,11 +332,6 @@ __global__ void emd_init_kernel(int B, int n, const float *__restrict__ xyz2,
       m[(2 * 16 + c) * 4 + q] = -2.f * z;
       m[(3 * 16 + c) * 4 + q] = tt;
     }
-    if (e < (long)B * kRankBins) {
-      ws.bins[0][e] = n / kRankBins;  // every bidder starts unassigned
-      ws.bins[1][e] = 0;
-    }
-    if (e < B) ws.far[e] = 0;
   }
 }
 
@@ -384,11 +391,13 @@ __global__ __launch_bounds__(256) void emd_sbbox_kernel(int B, int n, const floa
 __global__ __launch_bounds__(kThreads) void emd_seed_kernel(int B, int n,
                                                             const float *__restrict__ xyz1,
                                                             const float *__restrict__ xyz2,
-                                                            EmdWs ws) {
+                                                            EmdWs ws, const unsigned *__restrict__ rmask = nullptr) {
 #pragma clang fp contract(off)
+  if (rmask && rmask[kRecAny] == 0u) return;
   const long total = (long)B * n;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (long)gridDim.x * blockDim.x) {
+    if (rmask && !rmask[e / n]) continue;  // wave-uniform (n % 1024 == 0)
     // threads walk the bidders in sorted (Hilbert) order: neighbouring threads then read overlapping windows
     // of the target stream out of the L1 instead of 384 scattered bytes each
     const long bb = e / n;
@@ -633,7 +642,9 @@ __device__ __forceinline__ float coarse_threshold(float cm, float base, float a_
 //   * Every spin is bounded; a time-out raises ctl.abort and the device's sticky word, every workgroup of the
 //     launch leaves, the unfinished clouds get dist = NaN / assignment = -1, and the NEXT sn_emd_* / sn_mds call
 //     on the device -- or sn_device_status() at the caller's own sync point -- returns SN_ETIMEDOUT
-//     (SN_EMD_CHECK=1: the failing call itself synchronises and reports).
+//     (SN_EMD_CHECK=1: the failing call itself synchronises and reports).  Under SN_WAIT_RECOVER the sticky word is
+//     left alone (args.sticky = nullptr) and the recovery pass behind the launch recomputes those clouds
+//     (emd_recover_mark_kernel, sn_emd_forward).
 // =======================================================================================
 struct AuctionCtl {  // zeroed by a memset node before every launch
   unsigned ticket;
@@ -1474,6 +1485,7 @@ struct AuctionArgs {
   int prof;      // 1: record the execution window in the control block (sn_prof_enable)
   int skip_mode;     // contested-auction handling (outbid-skip + scan everywhere): 0 never, 1 when the lists say so (default), 2 always
   int spread_mode;   // interleaved rank split in scan iterations: 0 never, 1 default, 2 in every iteration
+  const unsigned *rmask;  // recovery pass (SN_WAIT_RECOVER, teams of one workgroup): only the marked clouds; nullptr: all
 };
 
 // The kernel's LDS, carved from the DYNAMIC segment on purpose: with a static 101 KB the compiler derives "one
@@ -1505,6 +1517,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   int *wsum = L.wsum;
   int &s_flag = L.s_flag, &s_ticket = L.s_ticket, &s_stray = L.s_stray;
   int *s_range = L.s_range, *s_bins = L.s_bins;
+  if (a.rmask && a.rmask[kRecAny] == 0u) return;  // recovery pass, nothing to recover: the whole grid leaves at once
   if (threadIdx.x == 0) {
     L.s_long = 0;
     L.s_skipped = 0;
@@ -1560,7 +1573,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   // keeps a CU from this launch, or a debugger): every workgroup of the launch leaves.  What it leaves behind must
   // not look like a result: the clouds this team had not finished get NaN distances and -1 assignments, the
   // device's sticky word makes the next sn_emd_* call fail (the reference returns an error code there,
-  // emd_cuda.cu:276-281).
+  // emd_cuda.cu:276-281).  The NaN / -1 rows are also the marker the recovery pass of SN_WAIT_RECOVER looks for.
   auto bail = [&](int b_from) {
     for (int b = b_from; b < a.B; b += a.tg.teams)
       for (int e = tid; e < n; e += kBidThreads) {
@@ -1612,6 +1625,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   if (a.diag && m == 0 && tid == 0 && loc) atomicAdd(reinterpret_cast<unsigned long long *>(a.dwords) + 12, 1ull);  // teams on one XCD
 
   for (int b = team; b < a.B; b += a.tg.teams) {
+    if (a.rmask && a.rmask[b] == 0u) continue;  // recovery pass: a cloud the team launch finished
     const size_t o = (size_t)b * n;
     float tmax = 0.f;
 #pragma unroll
@@ -2330,6 +2344,40 @@ __global__ void emd_exec_window_kernel(const AuctionCtl *ctl, unsigned long long
     acc[1] += 1ull;
   }
 }
+// SN_WAIT_RECOVER: the first step of the recovery pass behind the team launch, ONE workgroup.  Decides which clouds
+// the launch abandoned before anything rewrites their marker: with the launch's abort word clear none (the workgroup
+// leaves after one load); otherwise every cloud whose row holds a NaN distance with assignment -1 (what `bail`
+// writes; a finished cloud has finite distances unless its inputs hold NaN -- such a cloud is recomputed to the same
+// row).  rmask[b] = 1 for those, rmask[kRecAny] = their number, the device's "EMD recovered" counter grows by it.  It
+// then zeroes the first zero_words words of the control block (barrier and note blocks of the recovery launch, and
+// the abort word, which SN_EMD_CHECK reads afterwards); rmask lies behind them.
+__global__ __launch_bounds__(1024) void emd_recover_mark_kernel(int B, int n, const float *__restrict__ dist,
+                                                                const int *__restrict__ assignment, unsigned *ctl,
+                                                                unsigned *rmask, unsigned *recovered, int zero_words) {
+  const int tid = threadIdx.x;
+  if (__hip_atomic_load(&reinterpret_cast<AuctionCtl *>(ctl)->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+    if (tid == 0) rmask[kRecAny] = 0u;
+    return;
+  }
+  unsigned count = 0;
+  for (int b = 0; b < B; ++b) {
+    int lost = 0;
+    for (int e = tid; e < n && !lost; e += 1024) {
+      const size_t i = (size_t)b * n + e;
+      lost = __builtin_isnan(dist[i]) && assignment[i] < 0;
+    }
+    lost = __syncthreads_or(lost);
+    if (tid == 0) rmask[b] = lost ? 1u : 0u;
+    count += lost ? 1u : 0u;
+  }
+  __syncthreads();  // every thread has read the abort word
+  for (int i = tid; i < zero_words; i += 1024) ctl[i] = 0u;
+  if (tid == 0) {
+    rmask[kRecAny] = count;
+    if (count && recovered) __hip_atomic_fetch_add(recovered, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 std::mutex g_exec_mu;
 unsigned long long *g_exec_acc[64] = {nullptr};
 unsigned long long *exec_accumulator(int dev) {  // nullptr if it cannot be allocated (then nothing is recorded)
@@ -2432,6 +2480,11 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
   const char *safe_env = SN_KNOB("SN_EMD_SAFE");   // once per process; per call under SN_KNOBS_PER_CALL=1 (tests)
   int safe = safe_env && safe_env[0] == '1';
   unsigned *sticky = sn::sticky_device_word(dev);
+  // wait policy (sparenet_hip.h): `solo` = teams of one workgroup (nowait, or recover once the device's latch is set);
+  // `recover` = a team launch whose abandoned clouds the same call recomputes
+  const int policy = sn::wait_policy();
+  const bool solo = sn::wait_solo(dev);
+  const bool recover = policy == SN_WAIT_RECOVER && !solo;
   {
     std::lock_guard<std::mutex> lk(g_dev_mu);
     DeviceState &st = g_dev[dev];
@@ -2473,8 +2526,9 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
     args.dist = dist;
     args.ws = ws;
     args.ctl = static_cast<AuctionCtl *>(ws.ctl);
-    args.sticky = sticky;
+    args.sticky = policy == SN_WAIT_FAIL ? sticky : nullptr;
     args.safe = safe;
+    args.rmask = nullptr;
     args.stats = stats;
     static const int diag = [] { const char *e = getenv("SN_EMD_DIAG"); return e ? atoi(e) : 0; }();
     static const int gmax = [] { const char *e = getenv("SN_EMD_G"); const int v = e ? atoi(e) : 64; return v >= 1 ? v : 64; }();
@@ -2484,12 +2538,15 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
       const int v = e ? atoi(e) : SN_EMD_SCAN_MAX;
       args.scan_max = v < 0 ? 0 : v;
     }
-    args.tg = team_geometry(b, cus * kWgPerCu, gmax, legacy);
-    args.diag = diag;
+    args.tg = team_geometry(b, cus * kWgPerCu, solo ? 1 : gmax, legacy);
+    // the park knob (diag bit 3) parks a workgroup of a team-waiting launch; with teams of one workgroup that
+    // workgroup would be a whole team and its cloud unwritten: under recover / nowait such launches ignore it
+    args.diag = policy != SN_WAIT_FAIL && args.tg.G == 1 ? diag & ~8 : diag;
     static const int diag_m0 = [] { const char *e = getenv("SN_EMD_DIAG_M0"); return e ? atoi(e) : 0; }();
     args.diag_m0 = diag_m0;
     static const unsigned spin_env = [] { const char *e = getenv("SN_EMD_SPIN_LIMIT"); return e ? (unsigned)atol(e) : 0u; }();
-    args.spin_limit = (diag & 8) ? (1u << 15) : (spin_env ? spin_env : kSpinLimit);   // SN_EMD_SPIN_LIMIT: debugging aid
+    // SN_EMD_SPIN_LIMIT: debugging aid; set, it also holds for the park knob (a recovered call at a chosen limit)
+    args.spin_limit = spin_env ? spin_env : (args.diag & 8) ? (1u << 15) : kSpinLimit;
     args.dwords = reinterpret_cast<long long *>(static_cast<char *>(ws.ctl) + 4 * kCtlWords);
     {  // once per process; per call under SN_KNOBS_PER_CALL=1 (the tests compare the settings inside one process)
       const char *e = SN_KNOB("SN_EMD_SKIP");
@@ -2498,6 +2555,12 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
       args.spread_mode = e ? atoi(e) : 1;
     }
     SN_REQUIRE(args.tg.teams <= 1024, "sn_emd_forward: too many teams (%d)", args.tg.teams);
+    // the recovery pass: teams of one workgroup, its mask in the last kRecWords words of the control block, behind
+    // the barrier / note blocks of both launches
+    const TeamGeom rtg = team_geometry(b, cus * kWgPerCu, 1, legacy);
+    if (recover)
+      SN_REQUIRE(32 + 2 * 32 * (size_t)(args.tg.teams > rtg.teams ? args.tg.teams : rtg.teams) + kRecWords <= kCtlWords,
+                 "sn_emd_forward: too many teams (%d) for the recovery pass's mask", rtg.teams);
     if (diag) SN_HIP(hipMemsetAsync(args.dwords, 0, 8 * kDiagWords, s));
     SN_HIP(hipMemsetAsync(ws.ctl, 0, 4 * (32 + 2 * 32 * (size_t)args.tg.teams), s));   // barrier blocks + note blocks
     {
@@ -2516,8 +2579,27 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
       sn::PersistentLaunch chain(dev, s);  // never beside another team-waiting launch of this process (common.hpp)
       SN_TIMED("emd_auction", s, (emd_auction_kernel<<<cus * kWgPerCu, kBidThreads, sizeof(AuctionLds), s>>>(args)));
       if (args.prof) emd_exec_window_kernel<<<1, 1, 0, s>>>(args.ctl, exec_acc);
+      if (recover) {
+        // Recovery pass, no host synchronisation: mark the abandoned clouds, set them up again and run their auction
+        // with teams of one workgroup (the result does not depend on the geometry: bit-identical).  The sort's outputs
+        // (perm1 / tperm / hist / boxes, and sbbox) are functions of the inputs the auction only reads, so init and
+        // seed are what a cloud needs again (init rewrites `flags`, the sort's scratch use of it included).
+        unsigned *rmask = reinterpret_cast<unsigned *>(ws.ctl) + kCtlWords - kRecWords;
+        emd_recover_mark_kernel<<<1, 1024, 0, s>>>(b, n, dist, assignment, static_cast<unsigned *>(ws.ctl), rmask,
+                                                   sn::recovered_device_word(dev, sn::kRecoveredEmd),
+                                                   32 + 2 * 32 * rtg.teams);
+        emd_init_kernel<<<eblocks, kThreads, 0, s>>>(b, n, xyz2, assignment, ws, rmask);
+        emd_seed_kernel<<<eblocks, kThreads, 0, s>>>(b, n, xyz1, xyz2, ws, rmask);
+        AuctionArgs rargs = args;
+        rargs.tg = rtg;
+        rargs.sticky = nullptr;
+        rargs.diag = 0;
+        rargs.prof = 0;
+        rargs.rmask = rmask;
+        emd_auction_kernel<<<cus * kWgPerCu, kBidThreads, sizeof(AuctionLds), s>>>(rargs);
+      }
     }
-    if (check) {  // debugging aid: wait for the launch and report a time-out at once
+    if (check) {  // debugging aid: wait for the launch (and the recovery pass) and report a time-out at once
       unsigned abort_word = 0;
       SN_HIP(hipStreamSynchronize(s));
       SN_HIP(hipMemcpy(&abort_word, &args.ctl->abort, 4, hipMemcpyDeviceToHost));

@@ -245,9 +245,10 @@ template <int PPT>
 __global__ __launch_bounds__(1024) void mds_clustered_kernel(
     int n, int m, const float *__restrict__ xyz, const int *__restrict__ perm_all,
     const float *__restrict__ bbox, const float *__restrict__ mean_mst_length,
-    int *__restrict__ idxs, float team_ratio) {
+    int *__restrict__ idxs, float team_ratio, int recover, unsigned *recovered) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) float yz[];  // [PPT*1024][2], lane private
+  __shared__ int s_lost;
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float *__restrict__ p = xyz + (size_t)b * n * 3;
   const int *__restrict__ perm = perm_all + (size_t)b * n;
@@ -264,8 +265,18 @@ __global__ __launch_bounds__(1024) void mds_clustered_kernel(
     diag2 += ext * ext;
   }
   const bool fast_div = t >= 0x1p-40f && t <= 0x1p40f && diag2 * rt < 0x1p100f;
-  // dense regime (the cut ball covers most of the cloud): done by mds_dense_team_kernel when it was launched
-  if (team_ratio > 0.f && cut2 > team_ratio * diag2) return;
+  // dense regime (the cut ball covers most of the cloud): done by mds_dense_team_kernel when it was launched --
+  // unless its team gave up (SN_WAIT_RECOVER): a row that starts with -1 is taken over here and counted (the team
+  // writes index 0 first, and the whole row -1 when it gives up)
+  if (team_ratio > 0.f && cut2 > team_ratio * diag2) {
+    if (!recover) return;
+    if (tid == 0) {
+      s_lost = out[0] == -1;
+      if (s_lost && recovered) __hip_atomic_fetch_add(recovered, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __syncthreads();
+    if (!s_lost) return;
+  }
 
   float px[PPT], tmp[PPT];
   unsigned low[PPT];  // (bitrev10(k mod 1024) << 16) | (k << 1) | (k >= 8192), ~0 for padding
@@ -527,7 +538,8 @@ __global__ __launch_bounds__(1024) void mds_clustered_kernel(
 // Teams are formed from XCD-local tickets like the auction's (emd.hip): the G workgroups of a cloud sit on one
 // XCD whenever the dispatcher allows it, so the words travel through that XCD's L2; any placement is correct.
 // Every poll is bounded: on a time-out the launch raises its abort word and the device's sticky word (the next
-// sn_mds / sn_emd_* call fails with SN_ETIMEDOUT), and the cloud's whole index row is written as -1 (which
+// sn_mds / sn_emd_* call fails with SN_ETIMEDOUT; `sticky` is nullptr under SN_WAIT_RECOVER, where the one-workgroup
+// kernel behind this one samples the cloud instead), and the cloud's whole index row is written as -1 (which
 // sn_gather_forward turns into NaN features: never a plausible-looking sample).
 // Which clouds take this path: cut^2 > team_ratio x (bounding box diagonal)^2, the predicate by which the
 // single-workgroup kernel skips exactly those clouds; since round 6 team_ratio is ~0 for clouds of >= 8192 points on
@@ -1076,14 +1088,22 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
     // of config 5's clouds behind (171); a surface cloud at mean MST length 0.02 sits between 0.06 and 0.075 and is better
     // off on one workgroup (23.5 ms against 26-28 on a team), a trained generator's clouds are far below either.
     // profiles/r05_g_mds_team_ratio.txt)
-    static const float team_ratio = [] { const char *e = getenv("SN_MDS_RATIO"); const float v = e ? (float)atof(e) : 0.075f; return v > 0.f ? v : 0.075f; }();
+    const char *ratio_env = SN_KNOB("SN_MDS_RATIO");
+    const float ratio_v = ratio_env ? (float)atof(ratio_env) : 0.075f;
+    const float team_ratio = ratio_v > 0.f ? ratio_v : 0.075f;
     team_ratio_eff = team_ratio;
+    int recover = 0;
+    unsigned *recovered = nullptr;
     {
       int dev = 0, cus = 0;
       SN_HIP(hipGetDevice(&dev));
       if (const int rc = sn::check_sticky(dev, "sn_mds")) return rc;
       SN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-      static const int gmax = [] { const char *e = getenv("SN_MDS_G"); const int v = e ? atoi(e) : 32; return v >= 1 && v <= 32 ? v : 32; }();
+      const char *g_env = SN_KNOB("SN_MDS_G");
+      const int gmax = g_env && atoi(g_env) >= 1 && atoi(g_env) <= 32 ? atoi(g_env) : 32;
+      // wait policy (sparenet_hip.h): no teams under nowait or once the device's latch is set
+      const int policy = sn::wait_policy();
+      const bool solo = sn::wait_solo(dev);
       // A member owns PG x nw consecutive groups of 64 sorted points (nw <= 16 waves, PG register slots per lane): the
       // cloud's ceil(n / 64) groups are dealt out evenly.  (Rounds 3-5 dealt out whole slots of 1024 points: at n = 19384
       // and G = 16 ten members held two slots each and six held nothing.)  G = the largest power of two <= 32 such that
@@ -1097,16 +1117,21 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
         team_slots = 8 * tpx;
       }
       if (team_g >= 2 && sn::capturing(s)) team_g = 1;  // under graph capture: the one-workgroup kernel only
+      if (solo) team_g = 1;
       // Round 6: with several picks per exchange a team of >= 8 members beats the one-workgroup kernel in EVERY regime of
       // a SpareNet-sized cloud -- surface regime (mml 0.0085, 19384 -> 16384) 17.7 -> 10.6 ms at <= 8 clouds, 17.9 ->
       // 15.4 at 32; surface-like clouds 18.0-23.5 -> 10.6-12.2 (profiles/r06_h_mds_team_everywhere.txt) -- so such
       // clouds all go to teams; smaller clouds and teams keep the measured cross-over above.
-      if (team_g >= 8 && n >= 8192 && !getenv("SN_MDS_RATIO")) team_ratio_eff = 1e-30f;
+      if (team_g >= 8 && n >= 8192 && !ratio_env) team_ratio_eff = 1e-30f;
       if (team_g >= 2) {
         const int per_member = (groups + team_g - 1) / team_g;        // groups of 64 points a member owns
         const int pg = (per_member + 15) / 16;                        // register slots per lane
         const int nw = (per_member + pg - 1) / pg;                    // waves per member (<= 16)
-        unsigned *sticky = sn::sticky_device_word(dev);
+        unsigned *sticky = policy == SN_WAIT_FAIL ? sn::sticky_device_word(dev) : nullptr;
+        if (policy == SN_WAIT_RECOVER) {
+          recover = 1;
+          recovered = sn::recovered_device_word(dev, sn::kRecoveredMds);
+        }
         // SN_MDS_DIAG=8 (tests): the second member of cloud 0's team leaves at once and the polls give up early
         const char *dg = SN_KNOB("SN_MDS_DIAG");
         const bool park = dg && atoi(dg) == 8;
@@ -1140,7 +1165,8 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
        DataParallel), it is not a per-process fact */                                            \
     SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_clustered_kernel<P>),         \
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));  \
-    mds_clustered_kernel<P><<<b, 1024, lds, s>>>(n, m, xyz, perm, bbox, mean_mst_length, idx, skip_ratio); \
+    mds_clustered_kernel<P><<<b, 1024, lds, s>>>(n, m, xyz, perm, bbox, mean_mst_length, idx, skip_ratio, \
+                                                 recover, recovered);                                   \
   }
     // exact slot counts near the register limit (19 at SpareNet's n = 19384): every unused
     // slot costs three VGPRs and the 1024-lane workgroup only has 128 per lane
