@@ -286,8 +286,13 @@ int sn_p2i_max_backward(const float *out_grad, const int *out_ids,
  * are summed, which is what autograd does with the reference's per-radius calls).
  * out_grad / out_ids: nradii [batch,channels,h,w] tensors in the layout of the forward
  * (image_major as there); background_grad may be NULL (not wanted).  Pixel-centric:
- * every pixel adds its terms to its winner in 64-bit fixed point (integer atomics), so
- * the sums are exact and bit-reproducible. */
+ * every pixel adds its fp32 terms to its winner in 64-bit fixed point (integer atomics),
+ * so the sums are bit-reproducible.  The step is 2^(ilogb(m) - 43), m = max|out_grad| *
+ * max(1, max|feat| * pi / (2 min(radii)) * 1.01) over the finite values: a gradient of n
+ * terms is their exact sum to within n 2^-44 m, rounded once to fp32.  Non-finite terms
+ * are not added: a gradient with a NaN term, or with both a +inf and a -inf term, is NaN,
+ * one with only infinities of one sign is that infinity (the fp32 sum's result, in any
+ * order).  The workspace holds 8 bytes and one class byte per output entry. */
 size_t sn_p2i_max_backward_multi_workspace_bytes(int npoints, int channels);
 int sn_p2i_max_backward_multi(const float *out_grad, const int *out_ids,
                               const float *points, const float *feat,

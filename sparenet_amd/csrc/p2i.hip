@@ -1044,11 +1044,20 @@ int lin_blocks(long total) {
 // Every pixel that has a winner adds its three terms (d feature, d row, d col) to the winner's
 // accumulators.  fp32 atomics would make the sums depend on the arrival order; instead the
 // terms are converted to 64-bit fixed point (scale = a power of two chosen on the device from
-// max|out_grad| and max|feature|) and added with integer atomics -- integer addition is
-// associative, so the result is bit-reproducible, and it equals the exactly rounded sum of the
-// fp32 terms to ~2^-45 of the largest possible term.  The XCD-aware map keeps all pixels of an
-// image, hence all atomics on its points, inside one XCD's L2.
+// max|out_grad| and max|feature| over their FINITE values) and added with integer atomics --
+// integer addition is associative, so the result is bit-reproducible.  A sum of n terms equals
+// the exactly added fp32 terms to within n 2^-44 m (m: fixed_scale's bound on a term), rounded
+// once to fp32.  A term that is not finite skips the fixed point: it ORs its class (NaN, +inf,
+// -inf) into a byte per output entry and raises a flag word, and the finish kernel returns what
+// an fp32 sum of the terms returns (NaN for a NaN or for both infinities, else the infinity) --
+// order independent as well.  The XCD-aware map keeps all pixels of an image, hence all atomics
+// on its points, inside one XCD's L2.
 // ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float finite_abs(float x) {  // |x|, 0 for inf and NaN
+  const float a = __builtin_fabsf(x);
+  return a <= 3.40282347e38f ? a : 0.f;
+}
+
 __global__ __launch_bounds__(1024) void p2i_absmax_kernel(const float *__restrict__ a, long na,
                                                          const float *__restrict__ b, long nb,
                                                          unsigned *__restrict__ out2) {
@@ -1057,13 +1066,13 @@ __global__ __launch_bounds__(1024) void p2i_absmax_kernel(const float *__restric
   const long na4 = (reinterpret_cast<size_t>(a) & 15) == 0 ? na / 4 : 0;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < na4; e += (long)gridDim.x * blockDim.x) {
     const float4 v = reinterpret_cast<const float4 *>(a)[e];
-    ma = __builtin_fmaxf(__builtin_fmaxf(ma, __builtin_fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y))),
-                         __builtin_fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w)));
+    ma = __builtin_fmaxf(__builtin_fmaxf(ma, __builtin_fmaxf(finite_abs(v.x), finite_abs(v.y))),
+                         __builtin_fmaxf(finite_abs(v.z), finite_abs(v.w)));
   }
   for (long e = na4 * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; e < na; e += (long)gridDim.x * blockDim.x)
-    ma = __builtin_fmaxf(ma, __builtin_fabsf(a[e]));
+    ma = __builtin_fmaxf(ma, finite_abs(a[e]));
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < nb; e += (long)gridDim.x * blockDim.x)
-    mb = __builtin_fmaxf(mb, __builtin_fabsf(b[e]));
+    mb = __builtin_fmaxf(mb, finite_abs(b[e]));
   for (int m = 1; m < 64; m <<= 1) {
     ma = __builtin_fmaxf(ma, __shfl_xor(ma, m));
     mb = __builtin_fmaxf(mb, __shfl_xor(mb, m));
@@ -1085,12 +1094,24 @@ __global__ __launch_bounds__(1024) void p2i_absmax_kernel(const float *__restric
   }
 }
 
-// 2^e with every |term| * 2^e < 2^44 (sums of < 2^18 terms stay inside int64)
+// 2^e with every finite |term| * 2^e < 2^44 (sums of < 2^18 terms stay inside int64).  m in double: g and f are
+// finite, but their product can leave fp32 while every term is still finite.
 __device__ __forceinline__ double fixed_scale(const unsigned *absmax, float min_radius) {
-  const float g = __uint_as_float(absmax[0]), f = __uint_as_float(absmax[1]);
-  const float m = g * __builtin_fmaxf(1.f, f * (1.5707964f / min_radius) * 1.01f);
-  if (!(m > 0.f) || !(m < 3e38f)) return 1.0;
-  return ldexp(1.0, 43 - ilogbf(m));
+  const double g = __uint_as_float(absmax[0]), f = __uint_as_float(absmax[1]);
+  const double m = g * __builtin_fmax(1.0, f * (1.5707963267948966 / (double)min_radius) * 1.01);
+  if (!(m > 0.0)) return 1.0;  // no finite non-zero gradient: every finite term is 0
+  return ldexp(1.0, 43 - ilogb(m));
+}
+
+// the head of the backward's workspace: absmax[0] = max|out_grad|, [1] = max|feature| (bits), [2] = non-finite flag
+constexpr int kNonFiniteFlag = 2;
+// class bits of the non-finite terms of one output entry (one byte per entry, four per word)
+constexpr unsigned kClsNaN = 1u, kClsPosInf = 2u, kClsNegInf = 4u;
+
+__device__ __forceinline__ void mark_non_finite(unsigned *cls, unsigned *flag, long e, float v) {
+  const unsigned bits = v != v ? kClsNaN : (v > 0.f ? kClsPosInf : kClsNegInf);
+  atomicOr(cls + (e >> 2), bits << (8 * (e & 3)));
+  atomicOr(flag, 1u);
 }
 
 #ifndef SN_ACC_SLOTS
@@ -1116,9 +1137,9 @@ constexpr int kAccRegion = SN_ACC_REGION;
 __global__ __launch_bounds__(256) void p2i_max_bwd_accum_kernel(
     const float *__restrict__ out_grad, const int *__restrict__ out_ids,
     const float *__restrict__ points, const float *__restrict__ feat,
-    const unsigned *__restrict__ absmax, float *__restrict__ background_grad,
-    long long *__restrict__ acc_pts, long long *__restrict__ acc_feat, int channels, int batch,
-    int h, int w, RadiiArg ra, int nradii, float min_radius, long obstride, long orstride) {
+    unsigned *__restrict__ absmax, float *__restrict__ background_grad,
+    long long *__restrict__ acc_pts, long long *__restrict__ acc_feat, unsigned *__restrict__ cls, long npts2,
+    int channels, int batch, int h, int w, RadiiArg ra, int nradii, float min_radius, long obstride, long orstride) {
   // lane = pixel of an 8 x 8 tile.  Neighbouring pixels, and the radii of one pixel, often share their winner: the
   // terms first meet in the workgroup's LDS hash table keyed by the point id (LDS integer atomics), and every distinct
   // winner of the region then costs three global atomics.  XCD-aware: workgroup g runs on XCD g % 8 and only touches
@@ -1191,9 +1212,20 @@ __global__ __launch_bounds__(256) void p2i_max_bwd_accum_kernel(
             const float u = __builtin_fminf((dx * dx + dy * dy) * ra.inv_r2[k], 1.0f);
             const float cf = gk[k] * weight32(u);
             const float kk = gk[k] * fv * (4.93480220f * ra.inv_r2[k]) * slope32(u);  // pi^2 / 2
-            t0 = fixed(cf);
-            t1 = fixed(kk * dy);
-            t2 = fixed(kk * dx);
+            const float v1 = kk * dy, v2 = kk * dx;
+            if (__builtin_fabsf(cf) <= 3.40282347e38f && __builtin_fabsf(v1) <= 3.40282347e38f &&
+                __builtin_fabsf(v2) <= 3.40282347e38f) {
+              t0 = fixed(cf);
+              t1 = fixed(v1);
+              t2 = fixed(v2);
+            } else {  // rare: a non-finite term leaves its class, a finite one of the same pixel its fixed value
+              if (__builtin_fabsf(cf) <= 3.40282347e38f) t0 = fixed(cf);
+              else mark_non_finite(cls, absmax + kNonFiniteFlag, npts2 + (long)pid * channels + c, cf);
+              if (__builtin_fabsf(v1) <= 3.40282347e38f) t1 = fixed(v1);
+              else mark_non_finite(cls, absmax + kNonFiniteFlag, (long)pid * 2 + 0, v1);
+              if (__builtin_fabsf(v2) <= 3.40282347e38f) t2 = fixed(v2);
+              else mark_non_finite(cls, absmax + kNonFiniteFlag, (long)pid * 2 + 1, v2);
+            }
           }
         }
         if (pid >= 0 && pid == ppid) {  // the same winner as the previous radius: one table entry for both
@@ -1245,15 +1277,22 @@ __global__ __launch_bounds__(256) void p2i_max_bwd_accum_kernel(
 
 __global__ __launch_bounds__(256) void p2i_max_bwd_finish_kernel(
     const long long *__restrict__ acc_pts, const long long *__restrict__ acc_feat,
-    const unsigned *__restrict__ absmax, float *__restrict__ points_grad,
+    const unsigned *__restrict__ absmax, const unsigned *__restrict__ cls, float *__restrict__ points_grad,
     float *__restrict__ feat_grad, long npts2, long nfeat, float min_radius) {
   const double inv = 1.0 / fixed_scale(absmax, min_radius);
+  const bool non_finite = absmax[kNonFiniteFlag] != 0u;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < npts2 + nfeat;
        e += (long)gridDim.x * blockDim.x) {
+    float v = (float)((double)(e < npts2 ? acc_pts[e] : acc_feat[e - npts2]) * inv);
+    if (non_finite) {  // the fp32 sum of the terms: NaN with a NaN or with both infinities, else the infinity
+      const unsigned bits = (cls[e >> 2] >> (8 * (e & 3))) & 7u;
+      if ((bits & kClsNaN) || bits == (kClsPosInf | kClsNegInf)) v = __builtin_nanf("");
+      else if (bits) v = bits == kClsPosInf ? __builtin_inff() : -__builtin_inff();
+    }
     if (e < npts2)
-      points_grad[e] = (float)((double)acc_pts[e] * inv);
+      points_grad[e] = v;
     else
-      feat_grad[e - npts2] = (float)((double)acc_feat[e - npts2] * inv);
+      feat_grad[e - npts2] = v;
   }
 }
 
@@ -1504,7 +1543,8 @@ extern "C" int sn_p2i_max_backward(const float *out_grad, const int *out_ids, co
 
 extern "C" size_t sn_p2i_max_backward_multi_workspace_bytes(int npoints, int channels) {
   if (npoints < 0 || channels < 1) return 0;
-  return 256 + (size_t)npoints * (2 + (size_t)channels) * 8;
+  const size_t entries = (size_t)npoints * (2 + (size_t)channels);
+  return 256 + entries * 8 + sn::align_up(entries, 4);  // + one class byte per entry (non-finite terms)
 }
 
 extern "C" int sn_p2i_max_backward_multi(const float *out_grad, const int *out_ids,
@@ -1534,6 +1574,7 @@ extern "C" int sn_p2i_max_backward_multi(const float *out_grad, const int *out_i
   unsigned *absmax = static_cast<unsigned *>(workspace);
   long long *acc_pts = reinterpret_cast<long long *>(static_cast<char *>(workspace) + 256);
   long long *acc_feat = acc_pts + (size_t)npoints * 2;
+  unsigned *cls = reinterpret_cast<unsigned *>(acc_feat + (size_t)npoints * channels);
   SN_HIP(hipMemsetAsync(workspace, 0, sn_p2i_max_backward_multi_workspace_bytes(npoints, channels), s));
   p2i_absmax_kernel<<<512, 1024, 0, s>>>(out_grad, px * nradii, feat,
                                                            (long)npoints * channels, absmax);
@@ -1543,13 +1584,13 @@ extern "C" int sn_p2i_max_backward_multi(const float *out_grad, const int *out_i
   const long blocks = per_image * 8 * ((batch + 7) / 8);
   SN_REQUIRE(blocks < (1L << 31), "sn_p2i_max_backward_multi: image too large");
   p2i_max_bwd_accum_kernel<<<(int)blocks, 256, 0, s>>>(out_grad, out_ids, points, feat, absmax,
-                                                       background_grad, acc_pts, acc_feat, channels,
-                                                       batch, h, w, ra, nradii, rmin,
+                                                       background_grad, acc_pts, acc_feat, cls,
+                                                       (long)npoints * 2, channels, batch, h, w, ra, nradii, rmin,
                                                        image_major ? (long)nradii * channels * h * w : (long)channels * h * w,
                                                        image_major ? (long)channels * h * w : px);
   if (npoints > 0)
     p2i_max_bwd_finish_kernel<<<lin_blocks((long)npoints * (2 + channels)), 256, 0, s>>>(
-        acc_pts, acc_feat, absmax, points_grad, feat_grad, (long)npoints * 2,
+        acc_pts, acc_feat, absmax, cls, points_grad, feat_grad, (long)npoints * 2,
         (long)npoints * channels, rmin);
   return sn::launch_status("sn_p2i_max_backward_multi");
 }
