@@ -186,6 +186,47 @@ int sn_emd_backward(const float *xyz1, const float *xyz2,
                     const float *graddist, const int *assignment, int b, int n,
                     float *gradxyz1, void *stream);
 
+/* ------------------------------------------------------- EMD, any size n <= m
+ * The auction above for clouds of any size: xyz1[b,n,3] are the bidders, xyz2[b,m,3] the targets, 1 <= n <= m <= 2^20,
+ * b >= 1 (<= 65535).  dist[b,n] fp32, assignment[b,n] int32 (index into the cloud's m targets).  Per cloud and
+ * iteration, with cnt = the cloud's unassigned bidders:
+ *   block_cnt = ceil(n / 1024), unass_per_block = ceil(cnt / block_cnt), tpu = 1024 / unass_per_block;
+ *   Bid: a bidder scans the m targets in tiles of 2048, thread t of its tpu threads owning the contiguous chunk t of
+ *     every tile (delta = ceil(tile length / tpu)); d_k = (float)((3.0 - (double)sqrtf(s)) - (double)price[k]),
+ *     s = (dx*dx + dy*dy) + dz*dz rounded per operation, dx = target - query; best = max d, better = the second
+ *     element of the descending multiset of values (an exact tie gives better == best; both start at -1e9, so with
+ *     m = 1 better stays -1e9); best_i = argmin (thread(k), k) among the maximal values; increment =
+ *     (best - better) + eps, and the target's max_increment becomes the maximum of itself and the increments bid on it;
+ *   GetMax: among the bidders whose increment bi satisfies bi - 1e-6 <= mi <= bi + 1e-6 (double compare; mi = the
+ *     target's max_increment) the highest j writes max_idx[target].  max_idx is NOT cleared between iterations and
+ *     starts at 0, max_increment starts at 0;
+ *   Assign: a bidder with max_idx[target] == j -- every bidder in the last iteration -- takes its target (outside the
+ *     last iteration evicting its owner), price[target] += increment, max_increment[target] = -1e9;
+ *   CalcDist: dist[j] = (dx*dx + dy*dy) + dz*dz, dx = xyz1[j] - xyz2[assignment[j]]; with iters == 0 every
+ *     assignment is -1 and every dist 0.
+ * For n == m, n % 1024 == 0 this is exactly sn_emd_forward's contract, and such calls with b <= 512 ARE handed to
+ * sn_emd_forward (the persistent auction) unless SN_EMD_GENERAL=1 is set; every other call runs ordinary stream-ordered
+ * launches (three per iteration) in which no workgroup waits for another: no team, no time-out, no wait policy.
+ * stats as in sn_emd_forward (stats[0] += cnt * m per cloud and iteration).  Refused with SN_EINVAL: n > m (pass the
+ * smaller cloud first), m > 2^20, b < 1, a workspace smaller than sn_emd_general_workspace_bytes(b, n, m) (0 for
+ * invalid sizes). */
+size_t sn_emd_general_workspace_bytes(int b, int n, int m);
+int sn_emd_forward_general(const float *xyz1, const float *xyz2, int b, int n, int m,
+                           float eps, int iters, float *dist, int *assignment,
+                           void *workspace, size_t workspace_bytes,
+                           long long *stats, void *stream);
+/* gradxyz1[j] = 2 graddist[j] (xyz1[j] - xyz2[a(j)]) (the formula of sn_emd_backward), 0 where a(j) = -1 (or out of
+ * range); gradxyz2 (nullable; then workspace may be NULL) [b,m,3]: gradxyz2[k] = ((0 - t_j1) - t_j2) - ... in fp32 over
+ * the bidders j1 < j2 < ... with a(j) = k, t_j = gradxyz1[j]; 0 for a target nobody holds.  Several bidders share a
+ * target only through the last iteration's forced assignment (all but one of a group of identical bidders, for
+ * instance).  Both results are bit-reproducible; the work is linear in n + m however the bidders share targets.  The
+ * workspace is sized by sn_emd_general_backward_workspace_bytes(b, n, m) (0 for invalid sizes). */
+size_t sn_emd_general_backward_workspace_bytes(int b, int n, int m);
+int sn_emd_backward_general(const float *xyz1, const float *xyz2, const float *graddist,
+                            const int *assignment, int b, int n, int m, float *gradxyz1,
+                            float *gradxyz2, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
 /* -------------------------------------------------------- expansion penalty
  * replaces expansion_penalty.forward = expansion_penalty_forward
  *          (cuda/expansion_penalty/expansion_penalty.cpp:8-12,20;

@@ -1,0 +1,517 @@
+// emd_general.hip -- auction EMD for clouds of any size 1 <= n <= m (sn_emd_forward_general /
+// sn_emd_backward_general; semantics in include/sparenet_hip.h).
+//
+// The persistent auction of emd.hip is built around n == m, n % 1024 == 0: teams of workgroups own a cloud and wait
+// for each other inside one launch.  This path runs every phase as an ordinary stream-ordered launch, three per
+// iteration, and no workgroup ever waits for another:
+//   bid     every unassigned bidder scans all m targets and finds its top two bid values; the increment goes into the
+//           target's running maximum through an atomic max on an order-preserving integer key (increments can be
+//           negative when eps < 0);
+//   window  the bidders within +-1e-6 of their target's final maximum stamp the target's max_idx with an atomic max
+//           on (iteration << 32 | j): the highest j of this iteration wins, and a target nobody reached keeps its
+//           stale index (the reference never clears max_idx);
+//   assign  winners take their target and evict its previous owner; losers and the evicted append themselves to the
+//           next iteration's list (unordered: which position a bidder gets never enters a result).
+// The next iteration's unassigned count is final when its bid launch starts, so tpu -- and with it the tie rule of
+// the bid -- is read from a settled word.
+//
+// Bid (the hot path, O(cnt * m) per iteration): a workgroup stages tiles of 1024 targets {x, y, z, A'(price)} in
+// LDS; G lanes serve one bidder (G = 1 while the clouds have many bidders, up to a whole wave when few are left),
+// each lane scans every G-th target of the tile with the conservative fp32 filter of emd_bid.hpp, computes the exact
+// fp64-detour value only where the target can enter its top two, and the group merges its partial results with the
+// (thread(k), k) tie key.  The top-2 VALUES do not depend on the partition, and tie_key restores the reference's
+// index rule, so G is a pure performance choice.
+#include "common.hpp"
+#include "emd_bid.hpp"
+
+namespace {
+
+using namespace sn::emd;
+
+constexpr int kGThreads = 256;
+constexpr int kTile = 1024;             // targets per LDS tile (16 KiB)
+// lanes a bid launch aims for: 256 CUs x 4 SIMDs x 8 waves x 64.  Measured at B=32, 0.005 / 50 iterations (ms per
+// call, 16000 -> 16000 and 3000 -> 16384): 2^17 28.8 / 2.53, 2^18 21.7 / 2.27, 2^19 16.6 / 1.45, 2^20 16.3 / 1.51
+constexpr long kLanesWanted = 1L << 19;
+constexpr int kMaxEltBlocks = 2048;
+
+struct GenWs {
+  float *price;                 // [b, m]
+  int *assign_inv;              // [b, m] bidder holding the target, -1
+  unsigned *max_key;            // [b, m] running maximum increment, as inc_key
+  unsigned long long *max_idx;  // [b, m] (stamp << 32) | j of the window's winner; stamp = iteration + 1
+  int *bid;                     // [b, n] target of the bidder's last bid
+  float *bid_inc;               // [b, n] its increment
+  int *list[2];                 // [b, n] unassigned bidders of an iteration, any order
+  int *cnt[2];                  // [b]    their number
+};
+
+// order-preserving float -> unsigned (total order of the non-NaN floats; -0 sorts below +0)
+__device__ __forceinline__ unsigned inc_key(float v) {
+  const unsigned u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_inc(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// lanes per bidder: the power of two <= 64 that gives the launch about kLanesWanted lanes (every cloud is assumed to
+// have as many bidders as this one).  cnt * G < 2 * kLanesWanted / B whenever G > 1 (see bid_blocks).
+__host__ __device__ inline int group_lanes(int cnt, int B) {
+  const long want = kLanesWanted / ((long)B * cnt);
+  int G = 1;
+  while (G < 64 && G < want) G <<= 1;
+  return G;
+}
+
+// workgroups per cloud that cover cnt * group_lanes(cnt, B) lanes for every cnt <= n
+int bid_blocks(int B, int n) {
+  long lanes = 2 * kLanesWanted / B;
+  if (lanes > 64L * n) lanes = 64L * n;
+  if (lanes < n) lanes = n;
+  return (int)((lanes + kGThreads - 1) / kGThreads);
+}
+
+size_t carve_bytes(int b, int n, int m) {
+  const size_t tm = sn::align_up((size_t)b * m * 4, 256), tn = sn::align_up((size_t)b * n * 4, 256);
+  return 5 * tm + 4 * tn + 2 * sn::align_up((size_t)b * 4, 256);  // max_idx counts twice (8-byte words)
+}
+
+GenWs carve(void *workspace, int b, int n, int m) {
+  char *p = static_cast<char *>(workspace);
+  const size_t tm = sn::align_up((size_t)b * m * 4, 256), tn = sn::align_up((size_t)b * n * 4, 256);
+  GenWs w;
+  w.max_idx = reinterpret_cast<unsigned long long *>(p); p += 2 * tm;
+  w.price = reinterpret_cast<float *>(p); p += tm;
+  w.assign_inv = reinterpret_cast<int *>(p); p += tm;
+  w.max_key = reinterpret_cast<unsigned *>(p); p += tm;
+  w.bid = reinterpret_cast<int *>(p); p += tn;
+  w.bid_inc = reinterpret_cast<float *>(p); p += tn;
+  w.list[0] = reinterpret_cast<int *>(p); p += tn;
+  w.list[1] = reinterpret_cast<int *>(p); p += tn;
+  w.cnt[0] = reinterpret_cast<int *>(p); p += sn::align_up((size_t)b * 4, 256);
+  w.cnt[1] = reinterpret_cast<int *>(p);
+  return w;
+}
+
+int elt_blocks(long total) {
+  const long bl = (total + kGThreads - 1) / kGThreads;
+  return (int)(bl < kMaxEltBlocks ? bl : kMaxEltBlocks);
+}
+
+__global__ __launch_bounds__(kGThreads) void gen_init_kernel(int B, int n, int m, int *__restrict__ assignment, GenWs w) {
+  const long stride = (long)gridDim.x * blockDim.x, first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long e = first; e < (long)B * m; e += stride) {
+    w.price[e] = 0.f;
+    w.assign_inv[e] = -1;
+    w.max_key[e] = inc_key(0.f);  // max_increments starts at 0 (emd_module.py:49)
+    w.max_idx[e] = 0ull;          // ... and max_idx at 0: a stale index 0 from the start
+  }
+  for (long e = first; e < (long)B * n; e += stride) {
+    assignment[e] = -1;
+    w.list[0][e] = (int)(e % n);
+  }
+  for (long e = first; e < B; e += stride) {
+    w.cnt[0][e] = n;
+    w.cnt[1][e] = 0;
+  }
+}
+
+struct BidArgs {
+  int B, n, m, cur;
+  float eps;
+  const float *xyz1, *xyz2;
+  GenWs w;
+  long long *stats;
+};
+
+// grid (bid_blocks(B, n), B); lane l of cloud i serves bidder l / G with sub-lane l % G
+__global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
+  __shared__ float4 s_t[kTile];  // x, y, z, filter_target(price)
+  const int i = blockIdx.y, n = a.n, m = a.m;
+  const int cnt = a.w.cnt[a.cur][i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.w.cnt[a.cur ^ 1][i] = 0;  // this iteration's assign launch counts the next list into it
+    if (cnt > 0 && a.stats) {
+      atomicAdd(reinterpret_cast<unsigned long long *>(a.stats), (unsigned long long)cnt * m);
+      if (i == 0) atomicAdd(reinterpret_cast<unsigned long long *>(a.stats) + 1, 1ULL);
+    }
+  }
+  if (cnt == 0) return;
+  const int G = group_lanes(cnt, a.B);
+  const int first = blockIdx.x * kGThreads;
+  if (first / G >= cnt) return;  // uniform over the workgroup
+  const int lane = first + (int)threadIdx.x, u = lane / G, sub = lane & (G - 1);
+  const bool on = u < cnt;
+  // the reference's geometry: block_cnt = ceil(n / 1024) blocks share the cloud's bidders, tpu threads per bidder
+  const int block_cnt = (n + 1023) / 1024, per_block = (cnt + block_cnt - 1) / block_cnt;
+  const TieGeom g{m, 1024 / per_block};
+  int j = 0;
+  float x1 = 0.f, y1 = 0.f, z1 = 0.f;
+  if (on) {
+    j = a.w.list[a.cur][(size_t)i * n + u];
+    const float *p = a.xyz1 + ((size_t)i * n + j) * 3;
+    x1 = p[0];
+    y1 = p[1];
+    z1 = p[2];
+  }
+  const float *p2 = a.xyz2 + (size_t)i * m * 3;
+  const float *price = a.w.price + (size_t)i * m;
+  Top2 t = {-1e9f, -1e9f, -1, -1};
+  float cthr = filter_thr(t.better);
+  for (int k0 = 0; k0 < m; k0 += kTile) {
+    const int tn = m - k0 < kTile ? m - k0 : kTile;
+    __syncthreads();  // the previous tile is consumed
+    for (int c = threadIdx.x; c < tn; c += kGThreads) {
+      const float *q = p2 + (size_t)(k0 + c) * 3;
+      s_t[c] = make_float4(q[0], q[1], q[2], filter_target(price[k0 + c]));
+    }
+    __syncthreads();
+    if (on) {
+      for (int c = sub; c < tn; c += G) {
+        const float4 q = s_t[c];
+        if (filter_pass(sq_dist(q.x, q.y, q.z, x1, y1, z1), q.w, cthr)) {  // d_k may enter the top two
+          top2_push(t, bid_value(q.x, q.y, q.z, price[k0 + c], x1, y1, z1), k0 + c, g);
+          cthr = fmaxf(cthr, filter_thr(t.better));
+        }
+      }
+    }
+    if (G > 1) {
+      // the second largest of the group's partial top-2 values is a lower bound of the bidder's final `better`:
+      // every lane filters with it (a lane alone would see each of its m / G targets pass about 2 ln(m / G) times)
+      float b1 = t.best, b2 = t.better;
+      for (int off = 1; off < G; off <<= 1) {
+        const float o1 = __shfl_xor(b1, off), o2 = __shfl_xor(b2, off);
+        b2 = fmaxf(fminf(b1, o1), fmaxf(b2, o2));
+        b1 = fmaxf(b1, o1);
+      }
+      cthr = fmaxf(cthr, filter_thr(b2));
+    }
+  }
+  for (int off = 1; off < G; off <<= 1) {  // butterfly inside the group: every lane ends with the group's result
+    const float ob = __shfl_xor(t.best, off), obb = __shfl_xor(t.better, off);
+    const int oi = __shfl_xor(t.best_i, off), oi2 = __shfl_xor(t.better_i, off);
+    top2_merge(t, ob, obb, oi, oi2, g);
+  }
+  if (on && sub == 0) {
+    const float inc = t.best - t.better + a.eps;
+    const size_t o = (size_t)i * n + j;
+    a.w.bid[o] = t.best_i;
+    a.w.bid_inc[o] = inc;
+    if (t.best_i >= 0)  // -1 only for non-finite inputs: such a bidder never wins
+      atomicMax(&a.w.max_key[(size_t)i * m + t.best_i], inc_key(inc));
+  }
+}
+
+// grid (x, B): GetMax.  Every bidder inside the window of its target's maximum offers (stamp << 32) | j.
+__global__ __launch_bounds__(kGThreads) void emd_general_window_kernel(int n, int m, int cur, unsigned stamp, GenWs w) {
+  const int i = blockIdx.y;
+  const int cnt = w.cnt[cur][i];
+  for (int u = blockIdx.x * kGThreads + threadIdx.x; u < cnt; u += gridDim.x * kGThreads) {
+    const int j = w.list[cur][(size_t)i * n + u];
+    const int t = w.bid[(size_t)i * n + j];
+    if (t < 0) continue;
+    const size_t ot = (size_t)i * m + t;
+    if (in_window(w.bid_inc[(size_t)i * n + j], key_inc(w.max_key[ot])))
+      atomicMax(&w.max_idx[ot], ((unsigned long long)stamp << 32) | (unsigned)j);
+  }
+}
+
+// grid (x, B): Assign.  Bidders that stay or become unassigned go to the next list (wave-aggregated appends).
+__global__ __launch_bounds__(kGThreads) void emd_general_assign_kernel(int n, int m, int cur, int last, GenWs w,
+                                                                       int *__restrict__ assignment) {
+  const int i = blockIdx.y, lane = threadIdx.x & 63;
+  const int cnt = w.cnt[cur][i];
+  int *next_list = w.list[cur ^ 1] + (size_t)i * n;
+  int *next_cnt = &w.cnt[cur ^ 1][i];
+  for (int base = blockIdx.x * kGThreads; base < cnt; base += gridDim.x * kGThreads) {  // uniform over the workgroup
+    const int u = base + (int)threadIdx.x;
+    int push = -1;
+    if (u < cnt) {
+      const int j = w.list[cur][(size_t)i * n + u];
+      const int t = w.bid[(size_t)i * n + j];
+      const size_t ot = (size_t)i * m + t;
+      if (t >= 0 && (last || (int)(unsigned)w.max_idx[ot] == j)) {
+        // one winner per target outside the last iteration: the target's words have a single writer
+        assignment[(size_t)i * n + j] = t;
+        if (!last) {
+          const int inv = w.assign_inv[ot];
+          if (inv != -1) {
+            assignment[(size_t)i * n + inv] = -1;
+            push = inv;
+          }
+          w.assign_inv[ot] = j;
+          w.price[ot] += w.bid_inc[(size_t)i * n + j];
+          w.max_key[ot] = inc_key(-1e9f);
+        }
+      } else if (!last) {
+        push = j;
+      }
+    }
+    const unsigned long long mask = __ballot(push >= 0);
+    if (mask) {
+      const int leader = __ffsll((long long)mask) - 1;
+      int pos = 0;
+      if (lane == leader) pos = atomicAdd(next_cnt, __popcll(mask));
+      pos = __shfl(pos, leader);
+      if (push >= 0) next_list[pos + __popcll(mask & ((1ull << lane) - 1))] = push;
+    }
+  }
+}
+
+// CalcDist (emd_cuda.cu:217-226): xyz1 minus xyz2; an unassigned bidder (iters == 0) gets 0
+__global__ __launch_bounds__(kGThreads) void emd_general_dist_kernel(int B, int n, int m, const float *__restrict__ xyz1,
+                                                                     const float *__restrict__ xyz2,
+                                                                     const int *__restrict__ assignment,
+                                                                     float *__restrict__ dist) {
+#pragma clang fp contract(off)
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)B * n; e += (long)gridDim.x * blockDim.x) {
+    const int k = assignment[e];
+    if (k < 0) {
+      dist[e] = 0.f;
+      continue;
+    }
+    const float *p = xyz1 + e * 3, *q = xyz2 + ((e / n) * m + k) * 3;
+    const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+    dist[e] = dx * dx + dy * dy + dz * dz;
+  }
+}
+
+// ---- backward.  gradxyz1 per bidder; gradxyz2[k] = ((0 - t_j1) - t_j2) - ... over the bidders j1 < j2 < ... assigned
+// to k, t_j = gradxyz1[j].  The ascending-j sums go through a stable counting sort by target: count per target, an
+// exclusive scan per cloud, a stable scatter of the terms into each target's contiguous segment (chunks of 1024
+// bidders in ascending j, ranked inside a chunk by a bitonic sort of (target, j)), then one sequential fp32 sum per
+// segment.  Linear in n + m: a target shared by every bidder (a collapsed prediction) costs one pass over its segment.
+struct BwdWs {
+  int *count;   // [b, m] bidders per target
+  int *off;     // [b, m] exclusive prefix of count inside the cloud
+  int *run;     // [b, m] bidders of the target already placed by earlier chunks
+  float *terms; // [b, n, 3] gradxyz1 rows in (target, j) order
+};
+
+size_t bwd_bytes(int b, int n, int m) {
+  return 3 * sn::align_up((size_t)b * m * 4, 256) + sn::align_up((size_t)b * n * 12, 256);
+}
+
+BwdWs bwd_carve(void *workspace, int b, int n, int m) {
+  char *p = static_cast<char *>(workspace);
+  const size_t tm = sn::align_up((size_t)b * m * 4, 256);
+  BwdWs w;
+  w.count = reinterpret_cast<int *>(p); p += tm;
+  w.off = reinterpret_cast<int *>(p); p += tm;
+  w.run = reinterpret_cast<int *>(p); p += tm;
+  w.terms = reinterpret_cast<float *>(p);
+  return w;
+}
+
+// gradxyz1 (the formula of sn_emd_backward) and, when gradxyz2 is wanted, the bidders per target
+__global__ __launch_bounds__(kGThreads) void emd_general_bwd1_kernel(int B, int n, int m, const float *__restrict__ xyz1,
+                                                                     const float *__restrict__ xyz2,
+                                                                     const float *__restrict__ graddist,
+                                                                     const int *__restrict__ assignment,
+                                                                     float *__restrict__ grad1, int *count) {
+#pragma clang fp contract(off)
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)B * n; e += (long)gridDim.x * blockDim.x) {
+    const long c = e / n;
+    const int k = assignment[e];
+    if (k < 0 || k >= m) {  // unassigned (iters == 0); an index out of range is treated the same
+      grad1[e * 3 + 0] = grad1[e * 3 + 1] = grad1[e * 3 + 2] = 0.f;
+      continue;
+    }
+    const float *p = xyz1 + e * 3, *q = xyz2 + (c * m + k) * 3;
+    const float g = graddist[e] * 2;
+    grad1[e * 3 + 0] = g * (p[0] - q[0]);
+    grad1[e * 3 + 1] = g * (p[1] - q[1]);
+    grad1[e * 3 + 2] = g * (p[2] - q[2]);
+    if (count) atomicAdd(&count[c * m + k], 1);
+  }
+}
+
+constexpr int kSortThreads = 1024;
+
+// one workgroup per cloud: off = exclusive scan of count over the cloud's targets; run = 0
+__global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scan_kernel(int m, BwdWs w) {
+  __shared__ int s_wave[kSortThreads / 64];
+  __shared__ int s_carry;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t o = (size_t)blockIdx.x * m;
+  if (tid == 0) s_carry = 0;
+  __syncthreads();
+  for (int k0 = 0; k0 < m; k0 += kSortThreads) {
+    const int k = k0 + tid;
+    const int v = k < m ? w.count[o + k] : 0;
+    int incl = v;  // inclusive scan inside the wave
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(incl, d);
+      if (lane >= d) incl += t;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = s_carry;
+    for (int q = 0; q < wave; ++q) before += s_wave[q];
+    if (k < m) {
+      w.off[o + k] = before + incl - v;
+      w.run[o + k] = 0;
+    }
+    __syncthreads();
+    if (tid == kSortThreads - 1) s_carry = before + incl;
+    __syncthreads();
+  }
+}
+
+// one workgroup per cloud: the stable scatter.  Chunk after chunk of 1024 bidders in ascending j; the chunk's
+// (target << 10 | local j) keys are sorted (bitonic, in LDS), a bidder's rank among the chunk's bidders of its target is
+// its distance from the first key of the target, and the last of them advances the target's run.
+__global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scatter_kernel(int n, int m,
+                                                                               const int *__restrict__ assignment,
+                                                                               const float *__restrict__ grad1,
+                                                                               BwdWs w) {
+  __shared__ unsigned sk[kSortThreads];
+  const int tid = threadIdx.x;
+  const size_t c = blockIdx.x;
+  const unsigned kNone = 0xffffffffu;
+  for (int j0 = 0; j0 < n; j0 += kSortThreads) {
+    const int j = j0 + tid;
+    const int k = j < n ? assignment[c * n + j] : -1;
+    sk[tid] = (k >= 0 && k < m) ? ((unsigned)k << 10) | (unsigned)tid : kNone;  // k < 2^20: fits
+    __syncthreads();
+    for (int size = 2; size <= kSortThreads; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        const int partner = tid ^ stride;
+        if (partner > tid) {
+          const unsigned x = sk[tid], y = sk[partner];
+          if ((x > y) == ((tid & size) == 0)) {
+            sk[tid] = y;
+            sk[partner] = x;
+          }
+        }
+        __syncthreads();
+      }
+    const unsigned key = sk[tid];
+    int rank = 0, tk = 0;
+    if (key != kNone) {
+      tk = (int)(key >> 10);
+      int lo = 0, hi = tid;  // first position holding target tk
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((sk[mid] >> 10) < (unsigned)tk) lo = mid + 1; else hi = mid;
+      }
+      rank = tid - lo;
+      const size_t ot = c * m + tk;
+      const size_t pos = c * n + w.off[ot] + w.run[ot] + rank;
+      const size_t src = (c * n + j0 + (key & 1023u)) * 3;
+      w.terms[pos * 3 + 0] = grad1[src + 0];
+      w.terms[pos * 3 + 1] = grad1[src + 1];
+      w.terms[pos * 3 + 2] = grad1[src + 2];
+    }
+    __syncthreads();  // every rank of this chunk read run[] before it advances
+    if (key != kNone && (tid == kSortThreads - 1 || (sk[tid + 1] >> 10) != (unsigned)tk))
+      w.run[c * m + tk] += rank + 1;
+    __syncthreads();  // run[] and sk[] are reused by the next chunk
+  }
+}
+
+// one thread per target: the ascending-j sum over its segment
+__global__ __launch_bounds__(kGThreads) void emd_general_bwd_sum_kernel(int B, int n, int m, BwdWs w,
+                                                                        float *__restrict__ grad2) {
+#pragma clang fp contract(off)
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)B * m; e += (long)gridDim.x * blockDim.x) {
+    const long c = e / m;
+    const float *t = w.terms + (c * n + w.off[e]) * 3;
+    const int cnt = w.count[e];
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+#pragma unroll 4
+    for (int p = 0; p < cnt; ++p) {
+      sx = sx - t[p * 3 + 0];
+      sy = sy - t[p * 3 + 1];
+      sz = sz - t[p * 3 + 2];
+    }
+    grad2[e * 3 + 0] = sx;
+    grad2[e * 3 + 1] = sy;
+    grad2[e * 3 + 2] = sz;
+  }
+}
+
+bool persistent_shape(int b, int n, int m) { return n == m && n % 1024 == 0 && b <= 512; }
+
+}  // namespace
+
+extern "C" size_t sn_emd_general_workspace_bytes(int b, int n, int m) {
+  if (b < 1 || n < 1 || m < n) return 0;
+  const size_t own = carve_bytes(b, n, m);
+  if (!persistent_shape(b, n, m)) return own;
+  const size_t pers = sn_emd_workspace_bytes(b, n);  // the dispatch may hand the call to sn_emd_forward
+  return pers > own ? pers : own;
+}
+
+extern "C" int sn_emd_forward_general(const float *xyz1, const float *xyz2, int b, int n, int m, float eps, int iters,
+                                      float *dist, int *assignment, void *workspace, size_t workspace_bytes,
+                                      long long *stats, void *stream) {
+  SN_REQUIRE(xyz1 && xyz2 && dist && assignment && workspace, "sn_emd_forward_general: null pointer");
+  SN_REQUIRE(b >= 1 && b <= 65535, "sn_emd_forward_general: batch size must be in [1,65535] (got %d)", b);
+  SN_REQUIRE(n >= 1 && m >= 1, "sn_emd_forward_general: need n, m >= 1 (got n=%d, m=%d)", n, m);
+  SN_REQUIRE(n <= m, "sn_emd_forward_general: n=%d > m=%d: pass the smaller cloud first (xyz1 bids for xyz2)", n, m);
+  SN_REQUIRE(m <= (1 << 20), "sn_emd_forward_general: m must be <= 2^20 (got %d)", m);
+  SN_REQUIRE(iters >= 0, "sn_emd_forward_general: iters must be >= 0");
+  SN_REQUIRE(workspace_bytes >= sn_emd_general_workspace_bytes(b, n, m),
+             "sn_emd_forward_general: workspace too small (%zu < %zu)", workspace_bytes,
+             sn_emd_general_workspace_bytes(b, n, m));
+  {  // the shapes the persistent auction serves go there, unless SN_EMD_GENERAL=1
+    const char *e = SN_KNOB("SN_EMD_GENERAL");
+    if (!(e && e[0] == '1') && persistent_shape(b, n, m))
+      return sn_emd_forward(xyz1, xyz2, b, n, eps, iters, dist, assignment, workspace, workspace_bytes, stats, stream);
+  }
+  hipStream_t s = sn::as_stream(stream);
+  const GenWs w = carve(workspace, b, n, m);
+  gen_init_kernel<<<elt_blocks((long)b * (m > n ? m : n)), kGThreads, 0, s>>>(b, n, m, assignment, w);
+  BidArgs ba;
+  ba.B = b;
+  ba.n = n;
+  ba.m = m;
+  ba.eps = eps;
+  ba.xyz1 = xyz1;
+  ba.xyz2 = xyz2;
+  ba.w = w;
+  ba.stats = stats;
+  const dim3 bid_grid(bid_blocks(b, n), b);
+  int xb = (n + kGThreads - 1) / kGThreads;
+  const dim3 list_grid(xb < 64 ? xb : 64, b);
+  for (int it = 0; it < iters; ++it) {
+    const int cur = it & 1, last = it == iters - 1;
+    ba.cur = cur;
+    SN_TIMED("emd_general_bid", s, (emd_general_bid_kernel<<<bid_grid, kGThreads, 0, s>>>(ba)));
+    if (!last) emd_general_window_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, (unsigned)it + 1, w);
+    emd_general_assign_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, last, w, assignment);
+  }
+  emd_general_dist_kernel<<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, assignment, dist);
+  return sn::launch_status("sn_emd_forward_general");
+}
+
+extern "C" size_t sn_emd_general_backward_workspace_bytes(int b, int n, int m) {
+  if (b < 1 || n < 1 || m < n) return 0;
+  return bwd_bytes(b, n, m);
+}
+
+extern "C" int sn_emd_backward_general(const float *xyz1, const float *xyz2, const float *graddist,
+                                       const int *assignment, int b, int n, int m, float *gradxyz1, float *gradxyz2,
+                                       void *workspace, size_t workspace_bytes, void *stream) {
+  SN_REQUIRE(xyz1 && xyz2 && graddist && assignment && gradxyz1, "sn_emd_backward_general: null pointer");
+  SN_REQUIRE(b >= 1 && b <= 65535 && n >= 1 && n <= m && m <= (1 << 20),
+             "sn_emd_backward_general: need 1 <= b <= 65535, 1 <= n <= m <= 2^20 (got b=%d, n=%d, m=%d)", b, n, m);
+  hipStream_t s = sn::as_stream(stream);
+  BwdWs w{};
+  if (gradxyz2) {
+    SN_REQUIRE(workspace && workspace_bytes >= bwd_bytes(b, n, m),
+               "sn_emd_backward_general: workspace too small (%zu < %zu)", workspace_bytes, bwd_bytes(b, n, m));
+    w = bwd_carve(workspace, b, n, m);
+    SN_HIP(hipMemsetAsync(w.count, 0, (size_t)b * m * 4, s));
+  }
+  emd_general_bwd1_kernel<<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, graddist, assignment,
+                                                                        gradxyz1, w.count);
+  if (gradxyz2) {
+    emd_general_bwd_scan_kernel<<<b, kSortThreads, 0, s>>>(m, w);
+    emd_general_bwd_scatter_kernel<<<b, kSortThreads, 0, s>>>(n, m, assignment, gradxyz1, w);
+    emd_general_bwd_sum_kernel<<<elt_blocks((long)b * m), kGThreads, 0, s>>>(b, n, m, w, gradxyz2);
+  }
+  return sn::launch_status("sn_emd_backward_general");
+}

@@ -14,6 +14,7 @@ double on the same fp32 coordinates: the two can only disagree for |d - th| ~ 1e
 import torch
 
 from sparenet_amd.cuda.chamfer_distance.chamfer_distance import ChamferDistanceFunction
+from sparenet_amd.cuda.emd.emd_general import emd_general
 from sparenet_amd.cuda.emd.emd_module import emdModule
 
 
@@ -27,14 +28,20 @@ def f_score_from_chamfer(dist1, dist2, th=0.01):
                        torch.zeros_like(denom))
 
 
-def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, with_emd=True):
+def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, with_emd=True, emd_any_size=False):
     """pred [B,N,3], gt [B,M,3] on the GPU -> dict of per-sample tensors [B]:
     'F-Score', 'ChamferDistance' (x1000, mean dist1 + mean dist2, utils/misc.py:198-201 with
-    ChamferDistanceMean) and 'EMD' (x100; needs N == M, a multiple of 1024)."""
+    ChamferDistanceMean) and 'EMD' (x100; needs N == M, a multiple of 1024).
+    emd_any_size=True computes 'EMD' with emd_general for any N and M: the smaller cloud bids for the larger one
+    (pred when N == M, the same value as the default path for N == M a multiple of 1024) and the mean runs over it."""
     dist1, dist2 = ChamferDistanceFunction.apply(pred, gt)
     out = {"F-Score": f_score_from_chamfer(dist1, dist2, th),
            "ChamferDistance": (dist1.mean(dim=1) + dist2.mean(dim=1)) * 1000}
-    if with_emd:
+    if with_emd and emd_any_size:
+        small, large = (pred, gt) if pred.size(1) <= gt.size(1) else (gt, pred)
+        dist, _ = emd_general(small, large, emd_eps, emd_iters)
+        out["EMD"] = torch.sqrt(dist).mean(dim=1) * 100
+    elif with_emd:
         dist, _ = emdModule()(pred, gt, emd_eps, emd_iters)
         out["EMD"] = torch.sqrt(dist).mean(dim=1) * 100
     return out
