@@ -255,7 +255,11 @@ int sn_expansion_backward(const float *xyz, const float *graddist,
  * The `temp` tensor MDS.cpp:119-121 allocates lives in registers; only clouds
  * with more than 24576 points need `workspace` (sn_mds_workspace_bytes() > 0).
  * The density kernel is sn_expf (include/sn_expf.h), not libm/OCML expf.
- * Clouds of 2048 .. 19456 points are cluster-sorted and sampled either by one workgroup each or by a TEAM of up to
+ * Degenerate mean_mst_length (a collapsed coarse cloud): t = (float)(5 mml^2) may be 0 or subnormal.  -d/t is then
+ * evaluated as a correctly rounded IEEE quotient (no reciprocal shortcut): -inf for d > 0 and NaN for d = 0 when
+ * t = 0, and sn_expf(-inf) = sn_expf(NaN) = 0, so every density stays 0 and the tie order alone -- arg-min of
+ * (bitrev(k mod bs), k) -- picks the points.  (The reference's expf(NaN) = NaN poisons the density of every duplicate
+ * of the last pick instead; its order there is not reproduced.)  Clouds of 2048 .. 19456 points are cluster-sorted and sampled either by one workgroup each or by a TEAM of up to
  * 32 workgroups per cloud that takes several exact picks per exchange (every cloud of >= 8192 points when teams of
  * >= 8 fit the device; index sequences are the reference's either way).  A team's bounded waits can give up when the
  * device is shared with something that keeps compute units from the launch; the cloud's row is then -1, and by the

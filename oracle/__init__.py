@@ -320,7 +320,7 @@ def knn(x, k):
     models/sparenet_generator.py:872-875 up to the row constant) in float64, ascending, equal scores by
     lower index."""
     x = np.asarray(x, np.float64)
-    inner = np.einsum("bci,bcj->bij", x, x)
+    inner = np.matmul(x.transpose(0, 2, 1), x)    # (a BLAS product: einsum's own loop takes 40 s at C = 512, N = 3000)
     score = (x * x).sum(1)[:, None, :] - 2.0 * inner
     return np.argsort(score, axis=2, kind="stable")[:, :, :k]
 

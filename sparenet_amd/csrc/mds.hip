@@ -370,11 +370,12 @@ __global__ __launch_bounds__(1024) void mds_clustered_kernel(
   // then cost more than one scan of all slots, and the absorption bound excludes little.
   if (cut2 > 0.5f * diag2) {
     for (int j = 1; j < m; ++j) {
-      // which slots of this wave can receive a non-zero update?
+      // which slots of this wave can receive a non-zero update?  ('<=': the slot that holds the pick has gap 0 and
+      // must be visited to mark it taken, also when mean_mst_length = 0 makes the ball a point, far2 = 0)
       const float gx = __builtin_fmaxf(__builtin_fmaxf(blx - x1, x1 - bhx), 0.f);
       const float gy = __builtin_fmaxf(__builtin_fmaxf(bly - y1, y1 - bhy), 0.f);
       const float gz = __builtin_fmaxf(__builtin_fmaxf(blz - z1, z1 - bhz), 0.f);
-      const unsigned mask = (unsigned)__ballot((gx * gx + gy * gy) + gz * gz < far2);
+      const unsigned mask = (unsigned)__ballot((gx * gx + gy * gy) + gz * gz <= far2);
       unsigned mn = 0xffffffffu;  // densities are >= 0: their bit patterns order like the floats
   #pragma unroll
       for (int i = 0; i < PPT; ++i) {
@@ -462,7 +463,7 @@ __global__ __launch_bounds__(1024) void mds_clustered_kernel(
     const float gx = __builtin_fmaxf(__builtin_fmaxf(blx - x1, x1 - bhx), 0.f);
     const float gy = __builtin_fmaxf(__builtin_fmaxf(bly - y1, y1 - bhy), 0.f);
     const float gz = __builtin_fmaxf(__builtin_fmaxf(blz - z1, z1 - bhz), 0.f);
-    const unsigned mask = (unsigned)__ballot((gx * gx + gy * gy) + gz * gz < reach2);
+    const unsigned mask = (unsigned)__ballot((gx * gx + gy * gy) + gz * gz <= reach2);   // '<=': see above
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
       if ((mask >> i) & 1u) {  // wave-uniform
@@ -734,7 +735,7 @@ __global__ __launch_bounds__(1024) void mds_dense_team_kernel(
       const float gx = __builtin_fmaxf(__builtin_fmaxf(blx - x1, x1 - bhx), 0.f);
       const float gy = __builtin_fmaxf(__builtin_fmaxf(bly - y1, y1 - bhy), 0.f);
       const float gz = __builtin_fmaxf(__builtin_fmaxf(blz - z1, z1 - bhz), 0.f);
-      const unsigned mask = (unsigned)__ballot((gx * gx + gy * gy) + gz * gz < far2);
+      const unsigned mask = (unsigned)__ballot((gx * gx + gy * gy) + gz * gz <= far2);   // '<=': as in mds_clustered_kernel
 #pragma unroll
       for (int i = 0; i < PG; ++i) {
         if ((mask >> i) & 1u) {  // wave-uniform

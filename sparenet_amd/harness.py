@@ -92,6 +92,32 @@ class SurrogateGenerator(torch.nn.Module):
         return coarse, middle, refine, loss_mst
 
 
+class _EarlyLoss(torch.autograd.Function):
+    """(cloud, (leaf, loss, side)) -> loss, with loss = metric(leaf) computed on stream `side` from leaf =
+    cloud.detach() before cloud's other consumers were issued.  The autograd engine sums a tensor's incoming gradients
+    in the order of their nodes' creation; joined here, at the plain path's position, the metric's gradient reaches
+    `cloud` in that path's order.  (leaf and loss travel in a tuple: as inputs of their own the engine would also run
+    the metric's backward a second time, with a zero gradient.)"""
+
+    @staticmethod
+    def forward(ctx, cloud, early):
+        ctx.leaf, ctx.loss, ctx.side = early
+        return ctx.loss.detach().clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        # the metric's backward runs on the stream of its forward: order it explicitly after this stream's work (the
+        # incoming gradient) and this stream after it (the returned gradient)
+        main = torch.cuda.current_stream(grad.device)
+        ctx.side.wait_stream(main)
+        grad.record_stream(ctx.side)
+        with torch.cuda.stream(ctx.side):
+            (g,) = torch.autograd.grad(ctx.loss, ctx.leaf, grad, retain_graph=True)
+        main.wait_stream(ctx.side)
+        g.record_stream(main)
+        return g, None
+
+
 class Completion(torch.nn.Module):
     """runners/sparenet_runner.py:67-108."""
 
@@ -163,18 +189,21 @@ class Completion(torch.nn.Module):
         def on_cloud(cloud):
             cloud.record_stream(side)
             side.wait_stream(main)
+            # the loss of a detached copy: _EarlyLoss joins it to the cloud's graph below, where the plain path
+            # computes it, so that the cloud's gradient is summed in the plain path's order (bit-equal gradients)
+            leaf = cloud.detach().requires_grad_(cloud.requires_grad)
             with torch.cuda.stream(side):
-                loss = self._metric(cloud, gt)
+                loss = self._metric(leaf, gt)
             loss.record_stream(main)
-            early.append(loss)
+            early.append((cloud, leaf, loss))
 
         coarse, middle, refine, expansion_penalty = generator.forward_staged(partial, on_cloud)
+        main.wait_stream(side)
         if len(early) == 2:
-            coarse_loss, middle_loss = early
+            coarse_loss, middle_loss = (_EarlyLoss.apply(cloud, (leaf, loss, side)) for cloud, leaf, loss in early)
         else:   # a generator without refine stages hands nothing over early
             coarse_loss, middle_loss = self._metric(coarse, gt), self._metric(middle, gt)
         refine_loss = self._metric(refine, gt)
-        main.wait_stream(side)
         return self._compose(coarse, middle, refine, expansion_penalty, coarse_loss, middle_loss, refine_loss, gt)
 
     def _compose(self, coarse, middle, refine, expansion_penalty, coarse_loss, middle_loss, refine_loss, gt):

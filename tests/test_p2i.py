@@ -357,6 +357,24 @@ def test_hip_depthmaps_full_size_and_backward(dev):
     assert torch.isfinite(data.grad).all() and float(data.grad.abs().sum()) > 0
     tiny = cdm(data.detach(), view_id=0, radius_list=[0.02, 0.05])
     assert tiny.shape == (32, 2, 256, 256) and float((tiny > 0).float().mean()) < 0.01
+    # config 3's literal radii (pixels, so nearly every point covers at most one pixel) against the oracle, all views
+    from sparenet_amd.cuda.p2i_op import ext
+    from sparenet_amd.utils.p2i_utils import DepthProjectFunction
+
+    radii = [0.02, 0.05]
+    bi = torch.arange(32, dtype=torch.int32, device=dev).repeat_interleave(16384)
+    bg = torch.zeros(32, 1, 256, 256, device=dev)
+    for v in range(8):
+        maps = cdm(data.detach(), view_id=v, radius_list=radii)
+        pix, feat = DepthProjectFunction.apply(data.detach(), cdm._host_mats[v], 256)
+        out, ids = ext.p2i_max_forward_multi_gpu(pix, feat, bi, bg, 0, radii)
+        assert torch.equal(maps, out[:, :, 0].transpose(0, 1))      # what the module returns
+        pn, fn, bn = pix.cpu().numpy(), feat.cpu().numpy(), bi.cpu().numpy()
+        for r, R in enumerate(radii):
+            o, i = oracle.p2i_max_forward(pn, fn, bn, bg.cpu().numpy(), R, mt=True)
+            _close_maps(out[r].cpu().numpy(), ids[r].cpu().numpy(), o, i, f"config 3 view {v} R={R}", pn, fn,
+                        bg.cpu().numpy(), R)
+            assert (i >= 0).any(), (v, R)                              # the comparison is not over empty maps
 
 
 @pytest.mark.gpu
