@@ -405,6 +405,27 @@ int sn_graph_feature_backward(const float *grad_out, const long long *idx, int b
                               int c, int n, int k, float *grad_x, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------- PointNet feature pool (FPD)
+ * The per-point MLP of Frechet/pointnet.py (STN3d and PointNetfeat: conv 3 -> 64 -> 128 -> 1024) and its max over
+ * the points, fused (pointnet_pool.hip): xyz[b,n,3], trans[b,3,3] or NULL (identity), w1[64,3] b1[64], w2[128,64]
+ * b2[128], w3[1024,128] b3[1024] (eval-mode batch norm already folded into them by the caller), out[b,1024]:
+ *   x' = x . trans            (x'_j = fmaf(x2, t2j, fmaf(x1, t1j, x0 * t0j)); skipped for NULL)
+ *   h1 = relu(W1 x' + b1), h2 = relu(W2 h1 + b2)
+ *   out[cloud, j] = act(max over the points of (W3 h2)[j] + b3[j]),  act = ReLU if relu_last else identity
+ * fp32 throughout; the K = 64 and K = 128 layers run on v_mfma_f32_32x32x2_f32: every sum is a k-ordered fp32 fmaf
+ * chain (layers 1 and 2 start at the bias, layer 3 at 0; its bias and ReLU are applied once after the maximum, which
+ * is bit-identical because both are monotone).  The [128, n] and [1024, n] activations never reach global memory;
+ * tiles of 128 points are combined with a maximum, so the result does not depend on scheduling, on the order of the
+ * points or on the batch a cloud is in.  Inputs are expected to be finite (fmaxf drops a NaN, torch.max keeps it).
+ * Plain stream-ordered launches: no workgroup waits for another, no wait policy, may be captured into a graph.
+ * workspace: sn_pointnet_pool_workspace_bytes(b, n) (transposed weights and per-tile maxima; 0 for invalid sizes).
+ * Refused with SN_EINVAL: a null pointer (other than trans), b < 1, n < 1 or n > 2^20, a workspace too small. */
+size_t sn_pointnet_pool_workspace_bytes(int b, int n);
+int sn_pointnet_pool_forward(const float *xyz, const float *trans, const float *w1, const float *b1,
+                             const float *w2, const float *b2, const float *w3, const float *b3,
+                             int relu_last, int b, int n, float *out, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------- depth-map projection
  * The per-view glue of ComputeDepthMaps.forward (utils/p2i_utils.py:211-228 and the NDC ->
  * pixel rescale of cuda/p2i_op/__init__.py:117-121) fused into two small kernels each way:

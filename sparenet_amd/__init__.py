@@ -89,3 +89,17 @@ def alias_reference_modules():
     if utils_pkg is not None:                 # the reference's own `utils` package, already imported
         setattr(utils_pkg, "p2i_utils", amd_p2i)
     return amd_cuda
+
+
+def alias_frechet_modules():
+    """Make the reference's `from Frechet.FPD import calculate_fpd` / `from Frechet.pointnet import PointNetCls`
+    resolve to sparenet_amd.Frechet.  A separate opt-in from alias_reference_modules(): an evaluation script may
+    want one without the other.  Returns the package."""
+    import importlib
+    import sys
+
+    pkg = importlib.import_module("sparenet_amd.Frechet")
+    sys.modules["Frechet"] = pkg
+    for sub in ("FPD", "pointnet"):
+        sys.modules[f"Frechet.{sub}"] = importlib.import_module(f"sparenet_amd.Frechet.{sub}")
+    return pkg

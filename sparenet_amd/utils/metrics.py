@@ -45,3 +45,13 @@ def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, wit
         dist, _ = emdModule()(pred, gt, emd_eps, emd_iters)
         out["EMD"] = torch.sqrt(dist).mean(dim=1) * 100
     return out
+
+
+def fpd(pred, gt, model, batch_size=100):
+    """Frechet Point-cloud Distance of the SETS pred [N,n,3] and gt [M,m,3] (one scalar, float64) with `model`, a loaded
+    sparenet_amd.Frechet.pointnet.PointNetCls(k=16): calculate_fpd on the clouds' own device (the fused PointNet
+    kernel for CUDA tensors).  As in the reference the clouds after the last full batch of `batch_size` are dropped."""
+    from sparenet_amd.Frechet.FPD import calculate_fpd
+
+    device = pred.device if pred.is_cuda else None
+    return calculate_fpd(pred, gt, batch_size=batch_size, device=device, model=model)
