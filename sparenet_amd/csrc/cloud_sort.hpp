@@ -8,15 +8,11 @@
 #pragma once
 #include "common.hpp"
 
-// 16^3 cells.  32^3 (SN_SORT_BITS=5, 128 KB of counters) was measured: the blocks get no tighter for the
-// pruning tests at 16384 points and the sort itself costs more (Chamfer 0.58 -> 0.64 ms).
-#ifndef SN_SORT_BITS
-#define SN_SORT_BITS 4
-#endif
-
 namespace {
 
-constexpr int kSortBits = SN_SORT_BITS;          // grid side 2^bits per axis
+// 16^3 cells.  32^3 (5 bits, 128 KB of counters) was measured: the blocks get no tighter for the
+// pruning tests at 16384 points and the sort itself costs more (Chamfer 0.58 -> 0.64 ms).
+constexpr int kSortBits = 4;                     // grid side 2^bits per axis
 constexpr int kSortSide = 1 << kSortBits;
 constexpr int kSortCells = kSortSide * kSortSide * kSortSide;
 
@@ -34,13 +30,6 @@ __device__ __forceinline__ unsigned sort_coord(float v, float lo, float scale) {
 // which stretched the bounding boxes the pruning tests use.  (The name is kept: every caller only needs
 // "the sort key of a cell".)
 __device__ __forceinline__ unsigned morton3_4bit(unsigned x, unsigned y, unsigned z) {
-#ifdef SN_SORT_Z_ORDER
-  unsigned r = 0;
-#pragma unroll
-  for (int i = 0; i < kSortBits; ++i)
-    r |= (((x >> i) & 1u) << (3 * i)) | (((y >> i) & 1u) << (3 * i + 1)) | (((z >> i) & 1u) << (3 * i + 2));
-  return r;
-#else
   unsigned X[3] = {x, y, z};
 #pragma unroll
   for (unsigned q = 1u << (kSortBits - 1); q > 1u; q >>= 1) {
@@ -70,7 +59,6 @@ __device__ __forceinline__ unsigned morton3_4bit(unsigned x, unsigned y, unsigne
   for (int i = 0; i < kSortBits; ++i)
     r |= (((X[0] >> i) & 1u) << (3 * i + 2)) | (((X[1] >> i) & 1u) << (3 * i + 1)) | (((X[2] >> i) & 1u) << (3 * i));
   return r;
-#endif
 }
 
 // per cloud: bounding box -> cell histogram -> Hilbert-order permutation (one workgroup per cloud)

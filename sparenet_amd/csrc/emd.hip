@@ -58,9 +58,6 @@
 namespace {
 
 constexpr int kThreads = 256;     // element-wise kernels
-#ifndef SN_EMD_WAVES
-#define SN_EMD_WAVES 4
-#endif
 constexpr int kRankBins = 256;    // per cloud: counters of unassigned bidders per 1/256 of the Hilbert ranks
 // Recovery mask of SN_WAIT_RECOVER (emd_recover_mark_kernel): one word per cloud (b <= 512) + the number of marked
 // clouds at kRecAny, in the last kRecWords words of the control block (see sn_emd_forward for the bound)
@@ -365,16 +362,9 @@ struct BidOut {
   int skip;  // outbid-skip (see emit_bid): 0 = off
 };
 
-#ifndef SN_EMD_BIDWAVES
-#define SN_EMD_BIDWAVES 16   // waves per workgroup; 16 / SN_EMD_BIDWAVES workgroups share a CU
-#endif
-constexpr int kBidWaves = SN_EMD_BIDWAVES;
+constexpr int kBidWaves = 16;  // waves per workgroup
 constexpr int kBidThreads = kBidWaves * 64;
-#ifdef SN_EMD_WG_PER_CU   // experiment builds: e.g. ONE 8-wave workgroup per CU, half of every SIMD's registers left free
-constexpr int kWgPerCu = SN_EMD_WG_PER_CU;
-#else
-constexpr int kWgPerCu = 16 / kBidWaves;
-#endif
+constexpr int kWgPerCu = 1;    // 16 waves of 128 VGPRs fill a CU's register files: one workgroup per CU
 constexpr int kStash = kBidThreads;  // list slots whose bid is handed to the award phase through LDS
 
 // What the award phase needs to know about the bid of list slot u (written by the wave that emits the bid, read
@@ -420,11 +410,7 @@ __device__ __forceinline__ void emit_bid(const BidOut &A, size_t o, int j, int r
   const float inc = (top.best - top.better) + eps;
   stc(loc, &A.bid[o + j], top.best_i);
   stc(loc, &A.bid2[o + j], top.better_i == top.best_i ? -1 : top.better_i);
-#ifdef SN_EMD_NOSKIP
-  if (false) {
-#else
   if (A.skip) {
-#endif
     const float before = atomic_max_float_old(&A.max_inc[o + top.best_i], inc);
     if ((double)before > (double)inc + 1e-6) {  // outbid already: stays unassigned, bids again
       stc2(loc, &A.rec[4 * (o + rank)], __float_as_int(inc), kOutbid);
@@ -591,11 +577,10 @@ struct TeamGeom {
 //     idle: a late iteration is bound by the per-workgroup latency chain, not by the number of workgroups, and
 //     the cross-XCD team of 64 it replaces paid 2.7 us per barrier and coherent (fabric) stores.
 //   * otherwise (other partition modes, small devices): contiguous teams from one global counter.
-// gmax: upper bound on G (SN_EMD_G, experiments); legacy != 0: round 2's geometry (SN_EMD_GEOM=1).
-__host__ __device__ inline TeamGeom team_geometry(int B, int W, int gmax = 64, int legacy = 0) {
+// gmax: upper bound on G (1: teams of one workgroup, which wait for nobody -- the wait policy's solo and recovery launches).
+__host__ __device__ inline TeamGeom team_geometry(int B, int W, int gmax) {
   TeamGeom t;
-  const bool xcd_ok = W >= 64 && W % 64 == 0;
-  if (xcd_ok && (B >= 32 || !legacy)) {
+  if (W >= 64 && W % 64 == 0) {
     const int per = W / 8;                 // workgroups of one XCD
     const int tpx = (B + 7) / 8;           // teams an XCD must host so that every cloud has its own
     int g = 1;
@@ -688,6 +673,19 @@ struct BidCtx {
 #endif
 };
 
+// The SN_BID_STAMPS build's timers, shared by bid_group and bid_scan: st[i] collects the ticks spent up to STAMP(i)
+// since the previous stamp, or what COUNT(i, v) adds.
+#ifdef SN_BID_STAMPS
+#define STAMPS_BEGIN long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
+                     long long tk = (long long)__builtin_amdgcn_s_memrealtime();
+#define STAMP(i) { const long long now_ = (long long)__builtin_amdgcn_s_memrealtime(); st[i] += now_ - tk; tk = now_; }
+#define COUNT(i, v) st[i] += (v);
+#else
+#define STAMPS_BEGIN
+#define STAMP(i)
+#define COUNT(i, v)
+#endif
+
 // One group of 64 bidders, seen by one of its S segment-waves.
 __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc &ga, const int *lst,
                                           int count, int grp, int ngroups, int S, int seg, int lane) {
@@ -700,15 +698,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
   const float2 *pkc = c.pkc;
   Top2 top = {-1e9f, -1e9f, -1, -1};
   int j = 0;
-#ifdef SN_BID_STAMPS
-  long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long tk = (long long)__builtin_amdgcn_s_memrealtime();
-#define STAMP(i) { const long long now_ = (long long)__builtin_amdgcn_s_memrealtime(); st[i] += now_ - tk; tk = now_; }
-#define COUNT(i) st[i] += 1;
-#else
-#define STAMP(i)
-#define COUNT(i)
-#endif
+  STAMPS_BEGIN
   if (grp < ngroups && seg == 0) {  // wave-uniform: the group's first wave looks its bidders up
     const int2 jr = ldc2(&lst[2 * (active ? u : grp * 64)]);  // {bidder index, Morton rank}
     const int jj = jr.x;
@@ -822,7 +812,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
 #endif
       volatile int *own = T.owner;
       while (__any(pend)) {
-        COUNT(13)
+        COUNT(13, 1)
         asm volatile("" ::: "memory");
         if (pend) own[cc] = lane;
         if (pend && own[cc] == lane) {
@@ -895,7 +885,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
       }
       STAMP(1)
       while (todo) {
-        COUNT(6)
+        COUNT(6, 1)
         const int tl = __builtin_ctzll(todo);
         const int sb = ((t0 + tl) >> 2) * S + seg;
         todo &= todo - 1;
@@ -923,7 +913,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           if (!(gm & (0x1111u << g))) continue;
-          COUNT(8)
+          COUNT(8, 1)
           // all four blocks of the superblock once the subgroup reaches any of them: a skipped MFMA costs
           // a branch and four moves of "far" into its result registers on the vector ALU, which is the busy
           // unit here -- the matrix pipe is not (a block out of reach cannot produce a hit that matters)
@@ -941,10 +931,10 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
           if (__builtin_expect(__any(min16(d0, d1, d2, d3) <= thr[g]), 0)) {
             unsigned hm = hits4(d0, thr[g], 0) | hits4(d1, thr[g], 4) | hits4(d2, thr[g], 8) |
                           hits4(d3, thr[g], 12);
-            COUNT(9)
+            COUNT(9, 1)
             STAMP(2)
             while (__any(hm != 0)) {
-              COUNT(10)
+              COUNT(10, 1)
               const bool has = hm != 0;
               const int i = has ? __builtin_ctz(hm) : 0;
               hm &= hm - 1;
@@ -964,7 +954,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
                 STAMP(14)
                 batch(qcount, 64);
                 STAMP(3)
-                COUNT(7)
+                COUNT(7, 1)
                 drained = true;
               }
             }
@@ -1033,7 +1023,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
 // ---------------------------------------------------------------------------------------
 // Bid phase of a SPARSE iteration: one quarter wave (16 lanes) per bidder.
 //
-// Once a workgroup has at most SN_EMD_SCAN_MAX unassigned bidders they are far apart in their rank range: a
+// Once a workgroup has at most kScanMax unassigned bidders they are far apart in their rank range: a
 // group of 16 of them spans a third of the cloud, the union of their reaches (what bid_group's waves visit with the
 // matrix cores) is several times what any ONE of them can reach, and an iteration is a chain of dependent steps
 // (box tests -> ~9 visits -> hit queue -> merge of 16 segments) whose length, not whose work, sets the time.
@@ -1058,10 +1048,8 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
 // smaller bound only lets more through), and top2_push / top2_merge give the full scan's values and canonical
 // index in any order.
 // ---------------------------------------------------------------------------------------
-#ifndef SN_EMD_SCAN_MAX
-#define SN_EMD_SCAN_MAX 384  // bidders per workgroup up to which an iteration takes bid_scan (SN_EMD_SCAN overrides;
-                             // 128 / 256 / 384 / 512 / 1024: 2.24 / 2.10 / 2.07 / 2.07 / 2.08 ms per call at 32 clouds, r04)
-#endif
+constexpr int kScanMax = 384;  // bidders per workgroup up to which an iteration takes bid_scan (SN_EMD_SCAN overrides;
+                               // 128 / 256 / 384 / 512 / 1024: 2.24 / 2.10 / 2.07 / 2.07 / 2.08 ms per call at 32 clouds, r04)
 constexpr int kScanContested = 4096;  // bidders per workgroup up to which a CONTESTED iteration takes bid_scan (see the kernel)
 constexpr int kScanBlk = 1024;  // blocks of 16 targets whose boxes fit in the LDS copy (n <= 16384)
 constexpr int kScanList = 64;   // blocks within reach a quarter wave lists before it evaluates them
@@ -1093,12 +1081,7 @@ __device__ __forceinline__ bool box_within_priced(const f4 A, const f4 B, float 
 #define SN_DPP_F(v, ctrl) __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), ctrl, 0xf, 0xf, true))
 #define SN_DPP_I(v, ctrl) __builtin_amdgcn_mov_dpp(v, ctrl, 0xf, 0xf, true)
 
-#ifndef SN_EMD_BMIN_EVERY
-#define SN_EMD_BMIN_EVERY 4   // contested iterations between two refreshes of the boxes' price bounds
-#endif
-#ifndef SN_SCAN_RESHARE
-#define SN_SCAN_RESHARE 0  // > 0: the lanes share their bound again every that many rounds (see bid_scan)
-#endif
+constexpr int kBminEvery = 4;  // contested iterations between two refreshes of the boxes' price bounds
 constexpr int kRoundC = 4;  // blocks per round (two rounds are in flight: the register budget decides)
 struct ScanCand {  // one round of a quarter wave: lane c holds target c of each of the round's blocks
   f4 t[kRoundC];     // {x, y, z, index bits}
@@ -1115,17 +1098,7 @@ __device__ __forceinline__ void bid_scan(const BidCtx &c, ScanLds &SL, const int
   const f4 *t4 = c.t4;
   const float2 *pkc = c.pkc;
   unsigned short *lq = SL.list[wave][row];
-#undef STAMP
-#undef COUNT
-#ifdef SN_BID_STAMPS
-  long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long tk = (long long)__builtin_amdgcn_s_memrealtime();
-#define STAMP(i) { const long long now_ = (long long)__builtin_amdgcn_s_memrealtime(); st[i] += now_ - tk; tk = now_; }
-#define COUNT(i, v) st[i] += (v);
-#else
-#define STAMP(i)
-#define COUNT(i, v)
-#endif
+  STAMPS_BEGIN
   for (int u0 = 0; u0 < count;) {
     // T quarter waves per bidder: with few bidders left a bidder's superblocks are dealt out to 2 or 4 quarters
     const int rem = count - u0;
@@ -1240,9 +1213,6 @@ __device__ __forceinline__ void bid_scan(const BidCtx &c, ScanLds &SL, const int
 #undef SN_SHARE_STEP
       qlb = __builtin_fmaxf(qlb, m2);
     };
-#if SN_SCAN_RESHARE > 0
-    int rounds = 0;
-#endif
     do {
       // The blocks within reach into the lists of the team's quarters, dealt out in turn.  The blocks of the two
       // previous favourites go first: after the round that holds them the team knows two values near the final
@@ -1296,24 +1266,17 @@ __device__ __forceinline__ void bid_scan(const BidCtx &c, ScanLds &SL, const int
             first = false;
             share();
           }
-#if SN_SCAN_RESHARE > 0
-          else if ((++rounds % SN_SCAN_RESHARE) == 0) share();
-#endif
           i += kRoundC;
           if (!more) break;
           const bool more2 = __any(i + kRoundC < cnt);
           if (more2) fetch(A, i + kRoundC, cnt);
           process(B, i, cnt);
-#if SN_SCAN_RESHARE > 0
-          if ((++rounds % SN_SCAN_RESHARE) == 0) share();
-#endif
           i += kRoundC;
           if (!more2) break;
         }
       }
       first = false;
       asm volatile("" ::: "memory");
-#ifndef SN_SCAN_NO_RETIGHTEN
       // (Only on such data -- c.offsurf: on uniform clouds and on a prediction that lies on the targets' surface the
       // first reach is nearly the final one and the extra exchange cost 2 % of the call.)
       // A second SWEEP for the heaviest bidders (a wave instead of a quarter each, through a table in LDS) was
@@ -1332,7 +1295,6 @@ __device__ __forceinline__ void bid_scan(const BidCtx &c, ScanLds &SL, const int
         share();
         cthr = active ? filter_thr(__builtin_fmaxf(cm, qlb)) : cthr;
       }
-#endif
       STAMP(2)
     } while (__any(hm != 0ull));
     // the quarter's 16 partial results: xor 1, xor 2, mirror within 8, mirror within 16; then the team's quarters
@@ -1393,10 +1355,7 @@ struct AuctionArgs {
 
 // The kernel's LDS, carved from the DYNAMIC segment on purpose: with a static 101 KB the compiler derives "one
 // workgroup per CU = 4 waves per SIMD" from the LDS size and hands every wave 128 VGPRs whatever the occupancy
-// attributes say, which leaves no register for anybody else on the CU.  With SN_EMD_OCC waves per SIMD asked for
-// (5 -> 96 VGPRs) a quarter of every SIMD's register file stays free, and workgroups of OTHER launches (the
-// renderer's gather: 52 VGPRs, no LDS) run beside the auction in the issue slots its waves leave idle while they
-// wait (wait_frac 0.66).
+// attributes say.  Dynamic, the register budget is what emd_auction_kernel's attributes ask for.
 struct AuctionLds {
   WaveTab tabs[kBidWaves];
   GroupAcc gacc[kBidWaves];
@@ -1425,9 +1384,6 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
     L.s_long = 0;
     L.s_skipped = 0;
   }
-#ifdef SN_EMD_PRIO
-  __builtin_amdgcn_s_setprio(SN_EMD_PRIO);  // the chain of dependent steps goes first; co-resident waves fill the gaps
-#endif
   const int tid = threadIdx.x;
   if (tid < kBidWaves) {
     gacc[tid].lock = 0;
@@ -1648,11 +1604,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
         const bool spread = spread_ok && scan_ok &&
                             (a.spread_mode == 2 || ((a.spread_mode == 3 || (a.spread_mode == 1 && (contested || far))) &&
                                                     4 * total <= 3 * G * smax));
-#ifdef SN_EMD_NOSPREAD
-        if (false) {
-#else
         if (spread) {  // the same counters in transposed order (through LDS: a wave's own writes, in order)
-#endif
 #pragma unroll
           for (int q = 0; q < 4; ++q) s_bins[4 * lane + q] = v[q];
 #pragma unroll
@@ -1723,11 +1675,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
           // word w of the workgroup's positions: position p0 + w / wpb, i.e. bin p (contiguous) or its transpose
           int rw = r0 + 4 * w;
           if (w < vec) {  // coherent reads (other workgroups raised these flags), two 8-byte words per lane
-#ifdef SN_EMD_NOSPREAD
-            if (false) {
-#else
             if (spread) {
-#endif
               const int wsh = 31 - __builtin_clz((unsigned)(binsize >> 2));
               rw = transposed_bin(p0 + (w >> wsh)) * binsize + 4 * (w & ((1 << wsh) - 1));
             }
@@ -1797,8 +1745,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
         c.offsurf = contested || far;
         const int scan_max = ((contested || far) && a.scan_max > 0 && a.scan_max < kScanContested) ? kScanContested : a.scan_max;
         if (scan_ok && Um <= scan_max) {  // uniform in the workgroup: a quarter wave per bidder
-#ifndef SN_EMD_NO_BMIN
-          if (contested && a.eps >= 0.f && it - bmin_it >= SN_EMD_BMIN_EVERY) {
+          if (contested && a.eps >= 0.f && it - bmin_it >= kBminEvery) {
             // CONTESTED clouds: every box's bound from the SMALLEST PRICE it holds now (prices do not move during a bid
             // phase).  A bidder there sits far from the surface, the near-side targets' prices have climbed, and with the
             // price floor's bound their blocks -- which it can no longer want -- stay within its reach.  The refresh
@@ -1821,9 +1768,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
               L.scan.hb[h][1].z = mx;
             }
             __syncthreads();
-          } else
-#endif
-          if (a.eps < 0.f) {  // prices may fall: this iteration's price floor for every box
+          } else if (a.eps < 0.f) {  // prices may fall: this iteration's price floor for every box
             for (int i = tid; i < 4 * nsb; i += kBidThreads) L.scan.blk[i][1].z = c.a_max;
             for (int h = tid; h < (nsb >> 2); h += kBidThreads) L.scan.hb[h][1].z = c.a_max;
             __syncthreads();
@@ -2012,11 +1957,9 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   if (a.prof && tid == 0) atomicMax(&a.ctl->t_last, (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
 
-#ifndef SN_EMD_WAVES_PER_EU
-#define SN_EMD_WAVES_PER_EU 4   // 128 VGPRs per wave: 16 waves of one workgroup fill a CU's register files
-#endif
+constexpr int kWavesPerSimd = 4;  // 128 VGPRs per wave: 16 waves of one workgroup fill a CU's register files
 __global__ __attribute__((amdgpu_flat_work_group_size(kBidThreads, kBidThreads),
-                          amdgpu_waves_per_eu(SN_EMD_WAVES_PER_EU, SN_EMD_WAVES_PER_EU))) void emd_auction_kernel(AuctionArgs a) {
+                          amdgpu_waves_per_eu(kWavesPerSimd, kWavesPerSimd))) void emd_auction_kernel(AuctionArgs a) {
   auction_body(a);
 }
 __global__ __launch_bounds__(kThreads) void emd_bwd_kernel(
@@ -2434,14 +2377,12 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
     args.rmask = nullptr;
     args.stats = stats;
     static const int diag = [] { const char *e = getenv("SN_EMD_DIAG"); return e ? atoi(e) : 0; }();
-    static const int gmax = [] { const char *e = getenv("SN_EMD_G"); const int v = e ? atoi(e) : 64; return v >= 1 ? v : 64; }();
-    static const int legacy = [] { const char *e = getenv("SN_EMD_GEOM"); return e && e[0] == '1' ? 1 : 0; }();
     {  // once per process; per call under SN_KNOBS_PER_CALL=1 (the tests compare the two bid paths inside one process)
       const char *e = SN_KNOB("SN_EMD_SCAN");
-      const int v = e ? atoi(e) : SN_EMD_SCAN_MAX;
+      const int v = e ? atoi(e) : kScanMax;
       args.scan_max = v < 0 ? 0 : v;
     }
-    args.tg = team_geometry(b, cus * kWgPerCu, solo ? 1 : gmax, legacy);
+    args.tg = team_geometry(b, cus * kWgPerCu, solo ? 1 : 64);
     // the park knob (diag bit 3) parks a workgroup of a team-waiting launch; with teams of one workgroup that
     // workgroup would be a whole team and its cloud unwritten: under recover / nowait such launches ignore it
     args.diag = policy != SN_WAIT_FAIL && args.tg.G == 1 ? diag & ~8 : diag;
@@ -2460,7 +2401,7 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
     SN_REQUIRE(args.tg.teams <= 1024, "sn_emd_forward: too many teams (%d)", args.tg.teams);
     // the recovery pass: teams of one workgroup, its mask in the last kRecWords words of the control block, behind
     // the barrier / note blocks of both launches
-    const TeamGeom rtg = team_geometry(b, cus * kWgPerCu, 1, legacy);
+    const TeamGeom rtg = team_geometry(b, cus * kWgPerCu, 1);
     if (recover)
       SN_REQUIRE(32 + 2 * 32 * (size_t)(args.tg.teams > rtg.teams ? args.tg.teams : rtg.teams) + kRecWords <= kCtlWords,
                  "sn_emd_forward: too many teams (%d) for the recovery pass's mask", rtg.teams);

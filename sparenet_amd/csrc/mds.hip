@@ -177,7 +177,7 @@ __global__ __launch_bounds__(1024) void mds_kernel(int n, int m, const float *__
 }
 
 // ---------------------------------------------------------------------------------------
-// Cluster-sorted variant (the production path for 2048 <= n <= 20352, e.g. SpareNet's 19384).
+// Cluster-sorted variant (the production path for 2048 <= n <= 19456, e.g. SpareNet's 19384).
 // exp(-d/t) is EXACTLY 0 (sn_expf) once d/t >= 104, i.e. outside a ball of radius
 // sqrt(104 t) around the last pick (0.19 for SpareNet's t): there the update is a no-op.
 // With the reference's ownership (lane tid owns k = tid, tid+1024, ...) every register slot
@@ -1183,15 +1183,12 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
     if (sn::prof_enabled()) sn::prof_end("mds", s);
     return sn::launch_status("sn_mds");
   }
-#define SN_MDS(P) mds_kernel<P, 0, 1024><<<b, 1024, 0, s>>>(n, m, xyz, mean_mst_length, idx, lg)
+  // What mds_use_clustered leaves to the one-workgroup kernel: n < 2048 (ppt <= 2) and n > 19456 (ppt >= 20) -- up to
+  // 20352 with y and z in LDS, up to 24576 with z in LDS, beyond that the generic kernel.
 #define SN_MDS_Z(P, C) \
   mds_kernel<P, C, 1024><<<b, 1024, (size_t)n * 4 * C, s>>>(n, m, xyz, mean_mst_length, idx, lg)
   if (bs < 1024) mds_kernel<2, 0, 0><<<b, bs, 0, s>>>(n, m, xyz, mean_mst_length, idx, lg);
-  else if (ppt <= 2) SN_MDS(2);
-  else if (ppt <= 4) SN_MDS(4);
-  else if (ppt <= 8) SN_MDS(8);
-  else if (ppt <= 12) SN_MDS(12);
-  else if (ppt <= 16) SN_MDS(16);
+  else if (ppt <= 2) SN_MDS_Z(2, 0);
   else if (ppt <= 20 && (size_t)n * 8 + 1024 <= 160 * 1024) {
     // y,z of 20480 points = 160 KiB minus the hand-off slots: opt in to the large LDS carve
     SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_kernel<20, 2, 1024>),
@@ -1208,7 +1205,6 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
     mds_kernel_generic<<<b, bs, 0, s>>>(n, m, xyz, mean_mst_length,
                                         static_cast<float *>(workspace), idx, lg);
   }
-#undef SN_MDS
 #undef SN_MDS_Z
   if (sn::prof_enabled()) sn::prof_end("mds", s);
   return sn::launch_status("sn_mds");

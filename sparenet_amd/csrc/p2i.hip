@@ -613,7 +613,6 @@ __global__ __launch_bounds__(256, 6) void p2i_gather_max_kernel(
     return beg < end;
   };
   const float fmaxv = __uint_as_float(*fmax_bits);
-#ifndef SN_P2I_NO_RINGS
   for (int ring = 0; ring <= ra.halo; ++ring) {
     if (ring >= 2) {  // can anything of this ring still matter?  (uniform values: one answer for the wave)
       const float g = (float)((ring - 1) * kCell);
@@ -631,14 +630,6 @@ __global__ __launch_bounds__(256, 6) void p2i_gather_max_kernel(
     for (int part = 0; part < 2; ++part) {
       int beg, end;
       if (!ring_range(ring, rstep, part, beg, end)) continue;  // wave-uniform
-#else
-  {
-   for (int step = 0; step <= 2 * ra.halo; ++step) {
-    const int nparts = step == 0 ? 3 : 1;
-    for (int part = 0; part < nparts; ++part) {
-      int beg, end;
-      if (!row_range(step, part, beg, end)) continue;  // wave-uniform
-#endif
       float4 rec_next = make_float4(0.f, 0.f, 0.f, 0.f);
       if (beg + lane < end) rec_next = srec[beg + lane];
       for (int base = beg; base < end; base += 64) {
@@ -1114,18 +1105,12 @@ __device__ __forceinline__ void mark_non_finite(unsigned *cls, unsigned *flag, l
   atomicOr(flag, 1u);
 }
 
-#ifndef SN_ACC_SLOTS
-#define SN_ACC_SLOTS 512
-#endif
-#ifndef SN_ACC_REGION
-#define SN_ACC_REGION 4   // tiles per side of a workgroup's region (4: 32 x 32 pixels)
-#endif
-constexpr int kAccSlots = SN_ACC_SLOTS;  // per-WORKGROUP hash table of the winners of a region (real regions of 32 x 32
+constexpr int kAccSlots = 512;           // per-WORKGROUP hash table of the winners of a region (real regions of 32 x 32
                                          // pixels hold ~120 distinct winners over three radii; a term that finds no slot
                                          // within kAccProbes steps goes straight to the global accumulators -- integer
                                          // sums are exact in any order): 14 KB of LDS, 8 workgroups per CU
 constexpr int kAccProbes = 8;
-constexpr int kAccRegion = SN_ACC_REGION;
+constexpr int kAccRegion = 4;  // tiles per side of a workgroup's region (4: 32 x 32 pixels)
 
 // One WORKGROUP per region of kAccRegion x kAccRegion tiles of 8 x 8 pixels (wave w walks down column w of the region:
 // at any time the four waves read four horizontally adjacent tiles), one hash table per workgroup, ONE flush per
@@ -1529,11 +1514,10 @@ extern "C" int sn_p2i_max_backward(const float *out_grad, const int *out_ids, co
 #define SN_BWD(L)                                                                            \
   p2i_max_bwd_points_kernel<L><<<(int)blocks, 256, 0, s>>>(out_ids, contrib, points, batch_inds, \
       points_grad, feat_grad, npoints, channels, batch, h, w, radius, px)
-    switch (lpp) {
+    switch (lpp) {  // lanes_per_point_gather gives 4, 8, 16 or 64
       case 4: SN_BWD(4); break;
       case 8: SN_BWD(8); break;
       case 16: SN_BWD(16); break;
-      case 32: SN_BWD(32); break;
       default: SN_BWD(64); break;
     }
 #undef SN_BWD

@@ -1,7 +1,7 @@
 // wave_dpp.hpp -- wave-uniform minima over the 64 lanes with the DPP modifier ON the v_min (gfx9 DPP controls:
 // four steps inside the rows of 16 lanes, row_bcast:15 / row_bcast:31 across them; lane 63 ends up with the minimum).
 // Six vector instructions + one v_readlane, where mov_dpp + min pairs, four v_readlane and three scalar minima took
-// fifteen (SN_WAVE_MIN_PLAIN restores that form for A/B).
+// fifteen.
 //
 // Hazards: nobody inserts wait states inside inline assembly -- the hazard recognizer cannot see a DPP there.
 //   * a DPP operand written by the previous VALU instruction needs 2 wait states  -> "s_nop 1" in front of every step;
@@ -25,16 +25,6 @@ __device__ __forceinline__ void dpp_assert_full_exec() {
 }
 
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-#ifdef SN_WAVE_MIN_PLAIN
-  auto mn = [](unsigned a, unsigned b) { return a < b ? a : b; };
-  v = mn(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, true));   // quad_perm 1,0,3,2
-  v = mn(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, true));   // quad_perm 2,3,0,1
-  v = mn(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xf, 0xf, true));  // row_half_mirror
-  v = mn(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xf, 0xf, true));  // row_mirror
-  const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16);
-  const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-  return mn(mn(a, b), mn(c, d));
-#else
   dpp_assert_full_exec();
   asm volatile("s_nop 4\n\tv_min_u32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "+v"(v));
   asm volatile("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "+v"(v));
@@ -43,7 +33,6 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
   asm volatile("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(v));
   asm volatile("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(v));
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-#endif
 }
 
 // the same for finite floats (the renderer's tile minimum)

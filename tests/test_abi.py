@@ -148,3 +148,37 @@ def test_every_python_call_passes_the_declared_number_of_arguments():
                         assert got == want, f"{os.path.join(dirpath, f)}: {name} called with {got} arguments, declared {want}"
                         checked += 1
     assert checked >= 40
+
+
+def _env_switches(root):
+    """(names the library reads, names of the INTEGRATION.md table's first column, text of INTEGRATION.md)."""
+    csrc = os.path.join(root, "sparenet_amd", "csrc")
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".hpp", ".h")):
+            read |= set(re.findall(r'(?:getenv|SN_KNOB)\(\s*"(SN_[A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
+    doc = open(os.path.join(root, "INTEGRATION.md")).read()
+    table = doc.split("## 5. Environment switches", 1)[1]
+    listed = set()
+    for row in re.findall(r"^\|.*\|$", table.replace("\\|", "/"), re.M):   # `\|` is an escaped bar inside a cell
+        listed |= set(re.findall(r"\bSN_[A-Z0-9_]+", row.split("|")[1]))
+    return read, listed, doc
+
+
+def _env_switch_drift(root):
+    read, listed, doc = _env_switches(root)
+    undocumented = sorted(n for n in read if not re.search(r"\b" + n + r"\b", doc))
+    py = "".join(open(os.path.join(root, "sparenet_amd", f)).read()
+                 for f in sorted(os.listdir(os.path.join(root, "sparenet_amd"))) if f.endswith(".py"))
+    unread = sorted(n for n in listed if n not in read and not re.search(r"\b" + n + r"\b", py))
+    return read, listed, undocumented, unread
+
+
+def test_environment_switches_match_the_integration_table():
+    """Every SN_* variable the library reads (getenv / SN_KNOB in sparenet_amd/csrc) appears in INTEGRATION.md, and
+    every SN_* name in the first column of its environment table is read in csrc or sparenet_amd/*.py: a switch
+    that is deleted leaves the table, a new one enters it."""
+    read, listed, undocumented, unread = _env_switch_drift(ROOT)
+    assert len(read) >= 10 and len(listed) >= 10, (sorted(read), sorted(listed))
+    assert not undocumented, f"read in sparenet_amd/csrc but not in INTEGRATION.md: {undocumented}"
+    assert not unread, f"in INTEGRATION.md's environment table but read nowhere: {unread}"
