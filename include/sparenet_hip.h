@@ -227,6 +227,64 @@ int sn_emd_backward_general(const float *xyz1, const float *xyz2, const float *g
                             float *gradxyz2, void *workspace, size_t workspace_bytes,
                             void *stream);
 
+/* ------------------------------------------------------------ ragged batches
+ * Chamfer and EMD for a batch whose clouds have different numbers of points.
+ *
+ * Contract.  A ragged batch is a dense fp32 tensor [b, n, 3] plus lengths[b] (int32, a DEVICE pointer like every other
+ * pointer here): the first lengths[i] rows of cloud i are its points, the rest is padding, 0 <= lengths[i] <= n (a value
+ * outside is held to that range, or makes an EMD cloud invalid: no length can address memory outside the cloud's rows).
+ *   - a padding row's value is never read into any result, NaN and Inf included;
+ *   - for a padding row distances are 0, indices and assignments -1, gradients 0;
+ *   - a cloud's valid rows get exactly what the dense entry point gives for that cloud alone (b = 1, the arrays cut to
+ *     its lengths), bit for bit: distances, indices, assignments and gradients.  The other clouds of the batch, their
+ *     lengths and the padded width n have no influence;
+ *   - Chamfer with an empty side (lengths1[i] == 0 or lengths2[i] == 0): the cloud's distances are 0, its indices -1
+ *     and its gradients 0, on both sides;
+ *   - EMD with lengths1[i] == 0 or lengths1[i] > lengths2[i] (an invalid cloud): its whole dist row is NaN, its
+ *     assignment row -1 and its gradients 0; no kernel touches the cloud's points.
+ * Every entry point runs on the caller's stream as ordinary launches, reads the lengths on the device only (no host
+ * synchronisation), and has no workgroup wait for another: no wait policy applies.  n and m below are the padded
+ * widths = the row strides of every array; grids are sized for them, and work past a cloud's length leaves at once.
+ *
+ * sn_pad_compact turns the reference's padding convention (cuda/chamfer_dist/__init__.py:27-31,
+ * cuda/gridding/__init__.py:41-47: a row whose coordinates sum to zero is padding) into this contract: per cloud the
+ * rows with (x + y) + z != 0 -- fp32, in this order, the expression sn_gridding_forward_padded applies; a NaN sum
+ * keeps the row -- move to the front of packed[b,n,3] in their order (a stable partition; one workgroup per cloud, any
+ * n), lengths[b] counts them, src[b,n] holds the original row of every packed row and -1 beyond the length, where
+ * packed is 0.  packed must not alias xyz.
+ * sn_pad_scatter_rows is its inverse for per-row values (the backward pass): rows[b,n,c] -> out[b,n,c] with
+ * out[i, src[i,p], :] = rows[i, p, :] for src[i,p] >= 0 and 0 in every other row; out is fully overwritten. */
+int sn_pad_compact(const float *xyz, int b, int n, float *packed, int *lengths, int *src, void *stream);
+int sn_pad_scatter_rows(const float *rows, const int *src, int b, int n, int c, float *out, void *stream);
+/* sn_chamfer_forward's all-pairs kernel with per-cloud query and target counts: xyz1[b,n,3] with lengths1[b],
+ * xyz2[b,m,3] with lengths2[b]; dist1/idx1 [b,n], dist2/idx2 [b,m], fully overwritten. */
+int sn_chamfer_forward_ragged(const float *xyz1, const float *xyz2, int b, int n, int m,
+                              const int *lengths1, const int *lengths2, float *dist1, int *idx1,
+                              float *dist2, int *idx2, void *stream);
+/* sn_chamfer_backward over the valid rows: the inverse lists hold valid rows only and are summed in the same ascending
+ * order, lists longer than 64 entries (collapsed predictions) by a workgroup as there.  gradxyz1 / gradxyz2 fully
+ * overwritten.  graddist values at padding rows are not read. */
+size_t sn_chamfer_backward_ragged_workspace_bytes(int b, int n, int m);
+int sn_chamfer_backward_ragged(const float *xyz1, const float *xyz2, const float *graddist1,
+                               const float *graddist2, const int *idx1, const int *idx2, int b, int n, int m,
+                               const int *lengths1, const int *lengths2, float *gradxyz1, float *gradxyz2,
+                               void *workspace, size_t workspace_bytes, void *stream);
+/* The stream-ordered auction of sn_emd_forward_general with n_i = lengths1[i] bidders and m_i = lengths2[i] targets per
+ * cloud: block_cnt = ceil(n_i / 1024) and tpu come from the cloud's own n_i.  The padded widths need not satisfy
+ * n <= m (1 <= n, m <= 2^20).  Never handed to the persistent auction, whatever the shapes.  dist / assignment [b,n];
+ * stats as in sn_emd_forward_general (stats[0] += cnt * m_i).  The backward is sn_emd_backward_general's (gradxyz2
+ * nullable, an ascending-j fp32 sum per target); rows beyond lengths1[i] and invalid clouds count as unassigned
+ * whatever `assignment` holds there, and their graddist is not read. */
+size_t sn_emd_ragged_workspace_bytes(int b, int n, int m);
+int sn_emd_forward_ragged(const float *xyz1, const float *xyz2, int b, int n, int m, const int *lengths1,
+                          const int *lengths2, float eps, int iters, float *dist, int *assignment,
+                          void *workspace, size_t workspace_bytes, long long *stats, void *stream);
+size_t sn_emd_ragged_backward_workspace_bytes(int b, int n, int m);
+int sn_emd_backward_ragged(const float *xyz1, const float *xyz2, const float *graddist,
+                           const int *assignment, int b, int n, int m, const int *lengths1,
+                           const int *lengths2, float *gradxyz1, float *gradxyz2, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* -------------------------------------------------------- expansion penalty
  * replaces expansion_penalty.forward = expansion_penalty_forward
  *          (cuda/expansion_penalty/expansion_penalty.cpp:8-12,20;

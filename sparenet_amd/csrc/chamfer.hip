@@ -64,10 +64,25 @@ __device__ __forceinline__ float dist1(float tx, float ty, float tz, float qx, f
   return s + zz;
 }
 
+// a cloud's point count from lengths[b], held to [0, width] so that no value a caller uploads can address outside the
+// cloud's rows
+__device__ __forceinline__ int ragged_len(const int *__restrict__ lengths, int b, int width) {
+  const int v = lengths[b];
+  return v < 0 ? 0 : (v > width ? width : v);
+}
+__device__ __forceinline__ const int *pick_lengths(int second, const int *l1, const int *l2) { return second ? l2 : l1; }
+
+// Len is empty for dense batches (sn_chamfer_forward: the instantiation has the kernel arguments and the code it
+// always had) or (const int *lengths1, const int *lengths2) for ragged ones (sn_chamfer_forward_ragged): N and M are
+// then the padded widths = the row strides, and every cloud searches its first lengths1[b] rows against its first
+// lengths2[b].  A query's result depends on its own cloud's valid rows only -- the target tiles and chunks are cut
+// from the target count -- so it is what the dense kernel gives for that cloud alone.
+template <class... Len>
 __global__ __launch_bounds__(kThreads) void chamfer_fwd_kernel(
     const float *__restrict__ xyz1, const float *__restrict__ xyz2, int B, int N, int M,
     float *__restrict__ dist1_out, int *__restrict__ idx1_out,
-    float *__restrict__ dist2_out, int *__restrict__ idx2_out, int nb1, int nb2, int nb_max) {
+    float *__restrict__ dist2_out, int *__restrict__ idx2_out, int nb1, int nb2, int nb_max, Len... len) {
+  constexpr bool kRagged = sizeof...(Len) != 0;
   __shared__ float4 tile[kTileF4];
 
   // ---- XCD-aware decode: block g runs on XCD g%8; all blocks of one target
@@ -82,15 +97,33 @@ __global__ __launch_bounds__(kThreads) void chamfer_fwd_kernel(
   const int dir = cloud & 1;
   if (blk >= (dir ? nb2 : nb1)) return;
 
-  const int nq = dir ? M : N;   // queries
-  const int nt = dir ? N : M;   // targets
-  const float *__restrict__ q = (dir ? xyz2 : xyz1) + (size_t)b * nq * 3;
-  const float *__restrict__ t = (dir ? xyz1 : xyz2) + (size_t)b * nt * 3;
-  float *__restrict__ dist_out = (dir ? dist2_out : dist1_out) + (size_t)b * nq;
-  int *__restrict__ idx_out = (dir ? idx2_out : idx1_out) + (size_t)b * nq;
+  const int wq = dir ? M : N;   // queries: row stride
+  const int wt = dir ? N : M;   // targets: row stride
+  int nq = wq, nt = wt;         // ... and how many of the rows are points
+  if constexpr (kRagged) {      // two wave-uniform loads per workgroup
+    nq = ragged_len(pick_lengths(dir, len...), b, wq);
+    nt = ragged_len(pick_lengths(dir ^ 1, len...), b, wt);
+  }
+  const float *__restrict__ q = (dir ? xyz2 : xyz1) + (size_t)b * wq * 3;
+  const float *__restrict__ t = (dir ? xyz1 : xyz2) + (size_t)b * wt * 3;
+  float *__restrict__ dist_out = (dir ? dist2_out : dist1_out) + (size_t)b * wq;
+  int *__restrict__ idx_out = (dir ? idx2_out : idx1_out) + (size_t)b * wq;
 
   const int tid = threadIdx.x;
   const int q0 = blk * kQPB + tid;
+  if constexpr (kRagged) {
+    if (blk * kQPB >= nq || nt == 0) {  // nothing but padding rows here, or an empty side: 0 / -1 and leave
+#pragma unroll
+      for (int i = 0; i < kQPL; ++i) {
+        const int j = q0 + i * kThreads;
+        if (j < wq) {
+          dist_out[j] = 0.f;
+          idx_out[j] = -1;
+        }
+      }
+      return;
+    }
+  }
 
   f2 qx[kQPL / 2], qy[kQPL / 2], qz[kQPL / 2];
 #pragma unroll
@@ -175,6 +208,12 @@ __global__ __launch_bounds__(kThreads) void chamfer_fwd_kernel(
 #pragma unroll
   for (int i = 0; i < kQPL; ++i) {
     const int j = q0 + i * kThreads;
+    if constexpr (kRagged) {
+      if (j >= nq && j < wq) {  // a padding row
+        dist_out[j] = 0.f;
+        idx_out[j] = -1;
+      }
+    }
     if (j >= nq) continue;
     const float x = qx[i >> 1][i & 1], y = qy[i >> 1][i & 1], z = qz[i >> 1][i & 1];
     const int k0 = bchunk[i] * kChunk;
@@ -219,17 +258,42 @@ struct BwdLists {
   int *longs;  // [1 + B (N + M) / 64]  count, then the global slots (b (N + M) + slot) of the lists > kLongList
 };
 
+// The backward kernels serve dense and ragged batches.  kRagged = false: every row is a point, n1 = N and n2 = M, the
+// code of sn_chamfer_backward as it always was.  kRagged = true (sn_chamfer_backward_ragged): N and M are the padded
+// widths = the strides of every array, cloud b has its first n1 = lengths1[b] / n2 = lengths2[b] rows; only those
+// vote, enter a list or get a gradient, the others get 0.  A cloud with an empty side has no valid row at all.
+struct CloudLen {
+  int n1, n2;
+};
+template <bool kRagged>
+__device__ __forceinline__ CloudLen cloud_len(const int *__restrict__ len1, const int *__restrict__ len2, int b, int N,
+                                              int M) {
+  if constexpr (kRagged) {
+    const int n1 = ragged_len(len1, b, N), n2 = ragged_len(len2, b, M);
+    return (n1 > 0 && n2 > 0) ? CloudLen{n1, n2} : CloudLen{0, 0};
+  } else {
+    return CloudLen{N, M};
+  }
+}
+
+template <bool kRagged>
 __global__ __launch_bounds__(256) void chamfer_bwd_count_kernel(const int *__restrict__ idx1,
                                                                const int *__restrict__ idx2, int B, int N,
-                                                               int M, int *__restrict__ cnt) {
+                                                               int M, int *__restrict__ cnt,
+                                                               const int *__restrict__ len1,
+                                                               const int *__restrict__ len2) {
   const long total1 = (long)B * N, total = total1 + (long)B * M;
   const int NM = N + M;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const bool second = e >= total1;
     const long f = second ? e - total1 : e;
     const int b = (int)(f / (second ? M : N));
+    const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
+    if constexpr (kRagged) {
+      if ((int)(f - (long)b * (second ? M : N)) >= (second ? L.n2 : L.n1)) continue;
+    }
     // a cloud-1 query j votes for cloud-2 point idx1[j] (slot N + idx1[j]); a cloud-2 query for slot idx2[k]
-    const int slot = second ? clamp_idx(idx2[f], N) : N + clamp_idx(idx1[f], M);
+    const int slot = second ? clamp_idx(idx2[f], L.n1) : N + clamp_idx(idx1[f], L.n2);
     atomicAdd(&cnt[(long)b * NM + slot], 1);
   }
 }
@@ -267,10 +331,13 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_scan_kernel(int NM, const in
   }
 }
 
+template <bool kRagged>
 __global__ __launch_bounds__(256) void chamfer_bwd_fill_kernel(const int *__restrict__ idx1,
                                                               const int *__restrict__ idx2, int B, int N,
                                                               int M, int *__restrict__ fill,
-                                                              int *__restrict__ list) {
+                                                              int *__restrict__ list,
+                                                              const int *__restrict__ len1,
+                                                              const int *__restrict__ len2) {
   const long total1 = (long)B * N, total = total1 + (long)B * M;
   const int NM = N + M;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
@@ -279,7 +346,11 @@ __global__ __launch_bounds__(256) void chamfer_bwd_fill_kernel(const int *__rest
     const int na = second ? M : N;
     const int b = (int)(f / na);
     const int self = (int)(f - (long)b * na);
-    const int slot = second ? clamp_idx(idx2[f], N) : N + clamp_idx(idx1[f], M);
+    const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
+    if constexpr (kRagged) {
+      if (self >= (second ? L.n2 : L.n1)) continue;
+    }
+    const int slot = second ? clamp_idx(idx2[f], L.n1) : N + clamp_idx(idx1[f], L.n2);
     const int pos = atomicAdd(&fill[(long)b * NM + slot], 1);
     list[(long)b * NM + pos] = self;
   }
@@ -290,20 +361,27 @@ __global__ __launch_bounds__(256) void chamfer_bwd_fill_kernel(const int *__rest
 // one 0.03).  Leaves cnt / off / list exactly as they do (the order inside a list is arbitrary either way: the
 // gather sorts every list).
 constexpr int kBwdLdsSlots = 36864;
+template <bool kRagged>
 __global__ __launch_bounds__(1024) void chamfer_bwd_lists_kernel(const int *__restrict__ idx1,
                                                                const int *__restrict__ idx2, int N, int M,
                                                                int *__restrict__ cnt, int *__restrict__ off,
-                                                               int *__restrict__ list, int *__restrict__ longs) {
+                                                               int *__restrict__ list, int *__restrict__ longs,
+                                                               const int *__restrict__ len1,
+                                                               const int *__restrict__ len2) {
   extern __shared__ int lc[];  // N + M counters, later the fill cursors
   __shared__ int wsum[16];
   __shared__ int carry;
   const int b = blockIdx.x, tid = threadIdx.x, NM = N + M;
   const long o = (long)b * NM;
   const int *i1 = idx1 + (long)b * N, *i2 = idx2 + (long)b * M;
+  const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
+  // a row that is a point of its cloud (every row of a dense batch)
+  auto valid = [&](int e) { return !kRagged || (e >= N ? e - N < L.n2 : e < L.n1); };
   for (int i = tid; i < NM; i += 1024) lc[i] = 0;
   if (tid == 0) carry = 0;
   __syncthreads();
-  for (int e = tid; e < NM; e += 1024) atomicAdd(&lc[e >= N ? clamp_idx(i2[e - N], N) : N + clamp_idx(i1[e], M)], 1);
+  for (int e = tid; e < NM; e += 1024)
+    if (valid(e)) atomicAdd(&lc[e >= N ? clamp_idx(i2[e - N], L.n1) : N + clamp_idx(i1[e], L.n2)], 1);
   __syncthreads();
   for (int base = 0; base < NM; base += 1024) {
     const int i = base + tid;
@@ -328,8 +406,9 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_lists_kernel(const int *__re
     __syncthreads();
   }
   for (int e = tid; e < NM; e += 1024) {
+    if (!valid(e)) continue;
     const bool second = e >= N;
-    const int pos = atomicAdd(&lc[second ? clamp_idx(i2[e - N], N) : N + clamp_idx(i1[e], M)], 1);
+    const int pos = atomicAdd(&lc[second ? clamp_idx(i2[e - N], L.n1) : N + clamp_idx(i1[e], L.n2)], 1);
     list[o + pos] = second ? e - N : e;
   }
 }
@@ -371,11 +450,13 @@ __device__ __forceinline__ void sort_ints(int *a, int n) {
   }
 }
 
+template <bool kRagged>
 __global__ __launch_bounds__(256) void chamfer_bwd_gather_kernel(
     const float *__restrict__ xyz1, const float *__restrict__ xyz2, const float *__restrict__ gd1,
     const float *__restrict__ gd2, const int *__restrict__ idx1, const int *__restrict__ idx2, int B, int N,
     int M, const int *__restrict__ cnt, const int *__restrict__ off, int *__restrict__ list,
-    float *__restrict__ g1, float *__restrict__ g2) {
+    float *__restrict__ g1, float *__restrict__ g2, const int *__restrict__ len1,
+    const int *__restrict__ len2) {
 #pragma clang fp contract(off)
   const long total1 = (long)B * N, total = total1 + (long)B * M;
   const int NM = N + M;
@@ -389,8 +470,16 @@ __global__ __launch_bounds__(256) void chamfer_bwd_gather_kernel(
     const float *o = second ? xyz1 : xyz2;   // the other cloud
     const float *gda = second ? gd2 : gd1, *gdo = second ? gd1 : gd2;
     const float *pa = a + f * 3;
+    const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
+    if constexpr (kRagged) {
+      if (self >= (second ? L.n2 : L.n1)) {  // a padding row, or a cloud with an empty side
+        float *out = (second ? g2 : g1) + f * 3;
+        out[0] = out[1] = out[2] = 0.f;
+        continue;
+      }
+    }
     // own term: g (me - my neighbour)
-    const int k = clamp_idx((second ? idx2 : idx1)[f], nb);
+    const int k = clamp_idx((second ? idx2 : idx1)[f], second ? L.n1 : L.n2);
     const float *po = o + ((long)b * nb + k) * 3;
     const float g = gda[f] * 2;
     const float own[3] = {g * (pa[0] - po[0]), g * (pa[1] - po[1]), g * (pa[2] - po[2])};
@@ -422,11 +511,13 @@ __global__ __launch_bounds__(256) void chamfer_bwd_gather_kernel(
 // Here a workgroup takes the list: bitonic sort in LDS, then the terms in ascending order -- products computed 64 at
 // a time by a wave, the three running sums kept by three lanes (the order of the additions is the CPU path's, so
 // the result stays bit-equal to it).
+template <bool kRagged>
 __global__ __launch_bounds__(256) void chamfer_bwd_long_kernel(
     const float *__restrict__ xyz1, const float *__restrict__ xyz2, const float *__restrict__ gd1,
     const float *__restrict__ gd2, const int *__restrict__ idx1, const int *__restrict__ idx2, int B, int N,
     int M, const int *__restrict__ cnt, const int *__restrict__ off, int *__restrict__ list,
-    const int *__restrict__ longs, float *__restrict__ g1, float *__restrict__ g2) {
+    const int *__restrict__ longs, float *__restrict__ g1, float *__restrict__ g2,
+    const int *__restrict__ len1, const int *__restrict__ len2) {
 #pragma clang fp contract(off)
   extern __shared__ int keys[];  // kLongSortCap ints
   __shared__ float terms[3][64];
@@ -471,7 +562,8 @@ __global__ __launch_bounds__(256) void chamfer_bwd_long_kernel(
       __syncthreads();
     }
     if (tid < 64) {  // wave 0: ordered accumulation
-      const int k = clamp_idx((second ? idx2 : idx1)[f], nb);
+      const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
+      const int k = clamp_idx((second ? idx2 : idx1)[f], second ? L.n1 : L.n2);
       const float *po = o + ((long)b * nb + k) * 3;
       const float g = gda[f] * 2;
       const float ax = tid < 3 ? pa[tid] : 0.f;
@@ -513,9 +605,27 @@ extern "C" int sn_chamfer_forward(const float *xyz1, const float *xyz2, int b, i
   const int clouds_per_xcd = sn::ceil_div(2 * b, 8);
   const int grid = 8 * clouds_per_xcd * nb_max;
   hipStream_t s = sn::as_stream(stream);
-  SN_TIMED("chamfer_fwd", s, (chamfer_fwd_kernel<<<grid, kThreads, 0, s>>>(
+  SN_TIMED("chamfer_fwd", s, (chamfer_fwd_kernel<><<<grid, kThreads, 0, s>>>(
       xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, nb1, nb2, nb_max)));
   return sn::launch_status("sn_chamfer_forward");
+}
+
+extern "C" int sn_chamfer_forward_ragged(const float *xyz1, const float *xyz2, int b, int n, int m,
+                                         const int *lengths1, const int *lengths2, float *dist1, int *idx1,
+                                         float *dist2, int *idx2, void *stream) {
+  SN_REQUIRE(xyz1 && xyz2 && lengths1 && lengths2 && dist1 && idx1 && dist2 && idx2,
+             "sn_chamfer_forward_ragged: null pointer");
+  SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "sn_chamfer_forward_ragged: need b,n,m >= 1 (got %d,%d,%d)", b, n, m);
+  SN_REQUIRE((long)b * n < (1L << 29) && (long)b * m < (1L << 29), "sn_chamfer_forward_ragged: too large");
+  // the grid covers the padded widths: a block past its cloud's length writes its padding rows and leaves
+  const int nb1 = sn::ceil_div(n, kQPB), nb2 = sn::ceil_div(m, kQPB);
+  const int nb_max = nb1 > nb2 ? nb1 : nb2;
+  const int clouds_per_xcd = sn::ceil_div(2 * b, 8);
+  const int grid = 8 * clouds_per_xcd * nb_max;
+  hipStream_t s = sn::as_stream(stream);
+  SN_TIMED("chamfer_fwd_ragged", s, (chamfer_fwd_kernel<const int *, const int *><<<grid, kThreads, 0, s>>>(
+      xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, nb1, nb2, nb_max, lengths1, lengths2)));
+  return sn::launch_status("sn_chamfer_forward_ragged");
 }
 
 extern "C" size_t sn_chamfer_backward_workspace_bytes(int b, int n, int m) {
@@ -524,16 +634,25 @@ extern "C" size_t sn_chamfer_backward_workspace_bytes(int b, int n, int m) {
   return 4 * arr + sn::align_up(arr / 64 + 256, 256);  // cnt, off, fill, list + the directory of the long lists
 }
 
-extern "C" int sn_chamfer_backward(const float *xyz1, const float *xyz2, const float *graddist1,
-                                   const float *graddist2, const int *idx1, const int *idx2,
-                                   int b, int n, int m, float *gradxyz1, float *gradxyz2,
-                                   void *workspace, size_t workspace_bytes, void *stream) {
-  SN_REQUIRE(xyz1 && xyz2 && graddist1 && graddist2 && idx1 && idx2 && gradxyz1 && gradxyz2 && workspace,
-             "sn_chamfer_backward: null pointer");
-  SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "sn_chamfer_backward: need b,n,m >= 1");
-  SN_REQUIRE((long)b * ((long)n + m) < (1L << 30), "sn_chamfer_backward: too large");
+extern "C" size_t sn_chamfer_backward_ragged_workspace_bytes(int b, int n, int m) {
+  return sn_chamfer_backward_workspace_bytes(b, n, m);  // the same arrays, laid out by the padded widths
+}
+
+namespace {
+
+// sn_chamfer_backward (kRagged = false, len1 = len2 = nullptr) and sn_chamfer_backward_ragged
+template <bool kRagged>
+int chamfer_backward(const char *what, const float *xyz1, const float *xyz2, const float *graddist1,
+                     const float *graddist2, const int *idx1, const int *idx2, int b, int n, int m,
+                     const int *len1, const int *len2, float *gradxyz1, float *gradxyz2, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+  SN_REQUIRE(xyz1 && xyz2 && graddist1 && graddist2 && idx1 && idx2 && gradxyz1 && gradxyz2 && workspace &&
+                 (!kRagged || (len1 && len2)),
+             "%s: null pointer", what);
+  SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "%s: need b,n,m >= 1", what);
+  SN_REQUIRE((long)b * ((long)n + m) < (1L << 30), "%s: too large", what);
   SN_REQUIRE(workspace_bytes >= sn_chamfer_backward_workspace_bytes(b, n, m),
-             "sn_chamfer_backward: workspace too small (%zu < %zu)", workspace_bytes,
+             "%s: workspace too small (%zu < %zu)", what, workspace_bytes,
              sn_chamfer_backward_workspace_bytes(b, n, m));
   const size_t arr = sn::align_up((size_t)b * ((size_t)n + m) * 4, 256);
   char *p = static_cast<char *>(workspace);
@@ -547,26 +666,47 @@ extern "C" int sn_chamfer_backward(const float *xyz1, const float *xyz2, const f
   long blocks = (total + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipStream_t s = sn::as_stream(stream);
-  SN_REFUSE_CAPTURE(s, "sn_chamfer_backward");
+  SN_REFUSE_CAPTURE_AS(s, what);
   SN_HIP(hipMemsetAsync(L.longs, 0, 4, s));
   const size_t lds = ((size_t)n + m) * 4;
   if (n + m <= kBwdLdsSlots &&
       (lds <= 48 * 1024 ||  // per call: the attribute belongs to the current device
-       hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_bwd_lists_kernel),
+       hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_bwd_lists_kernel<kRagged>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess)) {
-    chamfer_bwd_lists_kernel<<<b, 1024, lds, s>>>(idx1, idx2, n, m, L.cnt, L.off, L.list, L.longs);
+    chamfer_bwd_lists_kernel<kRagged><<<b, 1024, lds, s>>>(idx1, idx2, n, m, L.cnt, L.off, L.list, L.longs, len1,
+                                                          len2);
   } else {
     SN_HIP(hipMemsetAsync(L.cnt, 0, (size_t)b * ((size_t)n + m) * 4, s));
-    chamfer_bwd_count_kernel<<<(int)blocks, 256, 0, s>>>(idx1, idx2, b, n, m, L.cnt);
+    chamfer_bwd_count_kernel<kRagged><<<(int)blocks, 256, 0, s>>>(idx1, idx2, b, n, m, L.cnt, len1, len2);
     chamfer_bwd_scan_kernel<<<b, 1024, 0, s>>>(n + m, L.cnt, L.off, L.fill, L.longs);
-    chamfer_bwd_fill_kernel<<<(int)blocks, 256, 0, s>>>(idx1, idx2, b, n, m, L.fill, L.list);
+    chamfer_bwd_fill_kernel<kRagged><<<(int)blocks, 256, 0, s>>>(idx1, idx2, b, n, m, L.fill, L.list, len1, len2);
   }
-  chamfer_bwd_gather_kernel<<<(int)blocks, 256, 0, s>>>(xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m,
-                                                        L.cnt, L.off, L.list, gradxyz1, gradxyz2);
+  chamfer_bwd_gather_kernel<kRagged><<<(int)blocks, 256, 0, s>>>(xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n,
+                                                                m, L.cnt, L.off, L.list, gradxyz1, gradxyz2, len1,
+                                                                len2);
   // the lists beyond kLongList entries (none in a trained model: the kernel then reads one word and leaves)
-  SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_bwd_long_kernel),
+  SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_bwd_long_kernel<kRagged>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, kLongSortCap * 4));
-  chamfer_bwd_long_kernel<<<128, 256, kLongSortCap * 4, s>>>(xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m,
-                                                            L.cnt, L.off, L.list, L.longs, gradxyz1, gradxyz2);
-  return sn::launch_status("sn_chamfer_backward");
+  chamfer_bwd_long_kernel<kRagged><<<128, 256, kLongSortCap * 4, s>>>(xyz1, xyz2, graddist1, graddist2, idx1, idx2, b,
+                                                                     n, m, L.cnt, L.off, L.list, L.longs, gradxyz1,
+                                                                     gradxyz2, len1, len2);
+  return sn::launch_status(what);
+}
+
+}  // namespace
+
+extern "C" int sn_chamfer_backward(const float *xyz1, const float *xyz2, const float *graddist1,
+                                   const float *graddist2, const int *idx1, const int *idx2,
+                                   int b, int n, int m, float *gradxyz1, float *gradxyz2,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+  return chamfer_backward<false>("sn_chamfer_backward", xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m, nullptr,
+                                 nullptr, gradxyz1, gradxyz2, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sn_chamfer_backward_ragged(const float *xyz1, const float *xyz2, const float *graddist1,
+                                          const float *graddist2, const int *idx1, const int *idx2, int b, int n,
+                                          int m, const int *lengths1, const int *lengths2, float *gradxyz1,
+                                          float *gradxyz2, void *workspace, size_t workspace_bytes, void *stream) {
+  return chamfer_backward<true>("sn_chamfer_backward_ragged", xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m,
+                                lengths1, lengths2, gradxyz1, gradxyz2, workspace, workspace_bytes, stream);
 }

@@ -122,9 +122,13 @@ inline bool capture_allowed() {
 // auction's second replay runs into its barrier time-outs and the Chamfer kernels' replay through autograd dies with a
 // memory access fault, although the same launches are clean in eager mode with every input at the end of its
 // allocation (tools/oob_probe.py).  They refuse instead of producing a graph that misbehaves later.
-#define SN_REFUSE_CAPTURE(stream, what)                                                                     \
-  SN_REQUIRE(!sn::capturing(stream) || sn::capture_allowed(), what ": the stream is being captured into a HIP graph; this op does not " \
-                                           "replay correctly from a graph (see common.hpp) -- launch it eagerly")
+#define SN_CAPTURE_REFUSAL \
+  ": the stream is being captured into a HIP graph; this op does not replay correctly from a graph (see common.hpp) -- launch it eagerly"
+#define SN_REFUSE_CAPTURE(stream, what) \
+  SN_REQUIRE(!sn::capturing(stream) || sn::capture_allowed(), what SN_CAPTURE_REFUSAL)
+// the same for an entry point whose name is only known at run time (a body shared by two entry points)
+#define SN_REFUSE_CAPTURE_AS(stream, what) \
+  SN_REQUIRE(!sn::capturing(stream) || sn::capture_allowed(), "%s" SN_CAPTURE_REFUSAL, what)
 
 // Tuning / test knobs from the environment are read ONCE per process, at their first use -- unless
 // SN_KNOBS_PER_CALL=1 (tests/conftest.py sets it before the library is loaded: the tests switch knobs inside one

@@ -99,7 +99,28 @@ int elt_blocks(long total) {
   return (int)(bl < kMaxEltBlocks ? bl : kMaxEltBlocks);
 }
 
-__global__ __launch_bounds__(kGThreads) void gen_init_kernel(int B, int n, int m, int *__restrict__ assignment, GenWs w) {
+// Ragged batches (sn_emd_forward_ragged / sn_emd_backward_ragged): the kernels below take the padded widths as n and m
+// -- the strides of every array -- and cloud i has its first lengths1[i] rows as bidders and its first lengths2[i] rows
+// as targets.  Dense calls pass no lengths and kRagged = false: every row counts.
+struct Ragged {
+  const int *lengths1, *lengths2;
+};
+struct CloudSize {
+  int n, m;  // bidders and targets; n == 0: the cloud takes no part (ragged only: lengths1 == 0 or > lengths2)
+};
+template <bool kRagged>
+__device__ __forceinline__ CloudSize cloud_size(Ragged r, long i, int n, int m) {
+  if constexpr (kRagged) {
+    const int a = r.lengths1[i], b = r.lengths2[i];
+    return (a >= 1 && a <= b && a <= n && b <= m) ? CloudSize{a, b} : CloudSize{0, 0};
+  } else {
+    return CloudSize{n, m};
+  }
+}
+
+template <bool kRagged>
+__global__ __launch_bounds__(kGThreads) void gen_init_kernel(int B, int n, int m, int *__restrict__ assignment, GenWs w,
+                                                             Ragged r) {
   const long stride = (long)gridDim.x * blockDim.x, first = (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (long e = first; e < (long)B * m; e += stride) {
     w.price[e] = 0.f;
@@ -112,7 +133,7 @@ __global__ __launch_bounds__(kGThreads) void gen_init_kernel(int B, int n, int m
     w.list[0][e] = (int)(e % n);
   }
   for (long e = first; e < B; e += stride) {
-    w.cnt[0][e] = n;
+    w.cnt[0][e] = cloud_size<kRagged>(r, e, n, m).n;  // 0: no bid, window or assign launch touches the cloud
     w.cnt[1][e] = 0;
   }
 }
@@ -123,17 +144,20 @@ struct BidArgs {
   const float *xyz1, *xyz2;
   GenWs w;
   long long *stats;
+  Ragged r;
 };
 
 // grid (bid_blocks(B, n), B); lane l of cloud i serves bidder l / G with sub-lane l % G
+template <bool kRagged>
 __global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
   __shared__ float4 s_t[kTile];  // x, y, z, filter_target(price)
-  const int i = blockIdx.y, n = a.n, m = a.m;
+  const int i = blockIdx.y, n = a.n, m = a.m;  // strides
   const int cnt = a.w.cnt[a.cur][i];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     a.w.cnt[a.cur ^ 1][i] = 0;  // this iteration's assign launch counts the next list into it
     if (cnt > 0 && a.stats) {
-      atomicAdd(reinterpret_cast<unsigned long long *>(a.stats), (unsigned long long)cnt * m);
+      atomicAdd(reinterpret_cast<unsigned long long *>(a.stats),
+                (unsigned long long)cnt * cloud_size<kRagged>(a.r, i, n, m).m);
       if (i == 0) atomicAdd(reinterpret_cast<unsigned long long *>(a.stats) + 1, 1ULL);
     }
   }
@@ -144,8 +168,9 @@ __global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
   const int lane = first + (int)threadIdx.x, u = lane / G, sub = lane & (G - 1);
   const bool on = u < cnt;
   // the reference's geometry: block_cnt = ceil(n / 1024) blocks share the cloud's bidders, tpu threads per bidder
-  const int block_cnt = (n + 1023) / 1024, per_block = (cnt + block_cnt - 1) / block_cnt;
-  const TieGeom g{m, 1024 / per_block};
+  const CloudSize cs = cloud_size<kRagged>(a.r, i, n, m);  // cnt > 0: the cloud takes part
+  const int block_cnt = (cs.n + 1023) / 1024, per_block = (cnt + block_cnt - 1) / block_cnt;
+  const TieGeom g{cs.m, 1024 / per_block};
   int j = 0;
   float x1 = 0.f, y1 = 0.f, z1 = 0.f;
   if (on) {
@@ -159,8 +184,8 @@ __global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
   const float *price = a.w.price + (size_t)i * m;
   Top2 t = {-1e9f, -1e9f, -1, -1};
   float cthr = filter_thr(t.better);
-  for (int k0 = 0; k0 < m; k0 += kTile) {
-    const int tn = m - k0 < kTile ? m - k0 : kTile;
+  for (int k0 = 0; k0 < cs.m; k0 += kTile) {
+    const int tn = cs.m - k0 < kTile ? cs.m - k0 : kTile;
     __syncthreads();  // the previous tile is consumed
     for (int c = threadIdx.x; c < tn; c += kGThreads) {
       const float *q = p2 + (size_t)(k0 + c) * 3;
@@ -260,12 +285,19 @@ __global__ __launch_bounds__(kGThreads) void emd_general_assign_kernel(int n, in
 }
 
 // CalcDist (emd_cuda.cu:217-226): xyz1 minus xyz2; an unassigned bidder (iters == 0) gets 0
+template <bool kRagged>
 __global__ __launch_bounds__(kGThreads) void emd_general_dist_kernel(int B, int n, int m, const float *__restrict__ xyz1,
                                                                      const float *__restrict__ xyz2,
                                                                      const int *__restrict__ assignment,
-                                                                     float *__restrict__ dist) {
+                                                                     float *__restrict__ dist, Ragged r) {
 #pragma clang fp contract(off)
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)B * n; e += (long)gridDim.x * blockDim.x) {
+    if constexpr (kRagged) {
+      if (cloud_size<true>(r, e / n, n, m).n == 0) {  // no auction was held: the whole row says so
+        dist[e] = __builtin_nanf("");
+        continue;
+      }
+    }
     const int k = assignment[e];
     if (k < 0) {
       dist[e] = 0.f;
@@ -304,16 +336,27 @@ BwdWs bwd_carve(void *workspace, int b, int n, int m) {
   return w;
 }
 
+// the target bidder j of cloud c holds, -1 for none: a padding row or a cloud that takes no part holds none whatever
+// the assignment array says, and an index beyond the cloud's targets is treated the same
+template <bool kRagged>
+__device__ __forceinline__ int held_target(const int *__restrict__ assignment, long c, int j, int n, int m, Ragged r) {
+  const CloudSize cs = cloud_size<kRagged>(r, c, n, m);
+  if (j >= cs.n) return -1;
+  const int k = assignment[c * n + j];
+  return k < cs.m ? k : -1;
+}
+
 // gradxyz1 (the formula of sn_emd_backward) and, when gradxyz2 is wanted, the bidders per target
+template <bool kRagged>
 __global__ __launch_bounds__(kGThreads) void emd_general_bwd1_kernel(int B, int n, int m, const float *__restrict__ xyz1,
                                                                      const float *__restrict__ xyz2,
                                                                      const float *__restrict__ graddist,
                                                                      const int *__restrict__ assignment,
-                                                                     float *__restrict__ grad1, int *count) {
+                                                                     float *__restrict__ grad1, int *count, Ragged r) {
 #pragma clang fp contract(off)
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)B * n; e += (long)gridDim.x * blockDim.x) {
     const long c = e / n;
-    const int k = assignment[e];
+    const int k = kRagged ? held_target<kRagged>(assignment, c, (int)(e - c * n), n, m, r) : assignment[e];
     if (k < 0 || k >= m) {  // unassigned (iters == 0); an index out of range is treated the same
       grad1[e * 3 + 0] = grad1[e * 3 + 1] = grad1[e * 3 + 2] = 0.f;
       continue;
@@ -362,17 +405,18 @@ __global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scan_kernel(int 
 // one workgroup per cloud: the stable scatter.  Chunk after chunk of 1024 bidders in ascending j; the chunk's
 // (target << 10 | local j) keys are sorted (bitonic, in LDS), a bidder's rank among the chunk's bidders of its target is
 // its distance from the first key of the target, and the last of them advances the target's run.
+template <bool kRagged>
 __global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scatter_kernel(int n, int m,
                                                                                const int *__restrict__ assignment,
                                                                                const float *__restrict__ grad1,
-                                                                               BwdWs w) {
+                                                                               BwdWs w, Ragged r) {
   __shared__ unsigned sk[kSortThreads];
   const int tid = threadIdx.x;
   const size_t c = blockIdx.x;
   const unsigned kNone = 0xffffffffu;
   for (int j0 = 0; j0 < n; j0 += kSortThreads) {
     const int j = j0 + tid;
-    const int k = j < n ? assignment[c * n + j] : -1;
+    const int k = j >= n ? -1 : kRagged ? held_target<kRagged>(assignment, c, j, n, m, r) : assignment[c * n + j];
     sk[tid] = (k >= 0 && k < m) ? ((unsigned)k << 10) | (unsigned)tid : kNone;  // k < 2^20: fits
     __syncthreads();
     for (int size = 2; size <= kSortThreads; size <<= 1)
@@ -444,6 +488,65 @@ extern "C" size_t sn_emd_general_workspace_bytes(int b, int n, int m) {
   return pers > own ? pers : own;
 }
 
+namespace {
+
+// the stream-ordered auction: three launches per iteration, no workgroup waits for another
+template <bool kRagged>
+int forward_launches(const char *what, const float *xyz1, const float *xyz2, int b, int n, int m, Ragged r, float eps,
+                     int iters, float *dist, int *assignment, void *workspace, long long *stats, void *stream) {
+  hipStream_t s = sn::as_stream(stream);
+  const GenWs w = carve(workspace, b, n, m);
+  gen_init_kernel<kRagged><<<elt_blocks((long)b * (m > n ? m : n)), kGThreads, 0, s>>>(b, n, m, assignment, w, r);
+  BidArgs ba;
+  ba.B = b;
+  ba.n = n;
+  ba.m = m;
+  ba.eps = eps;
+  ba.xyz1 = xyz1;
+  ba.xyz2 = xyz2;
+  ba.w = w;
+  ba.stats = stats;
+  ba.r = r;
+  const dim3 bid_grid(bid_blocks(b, n), b);
+  int xb = (n + kGThreads - 1) / kGThreads;
+  const dim3 list_grid(xb < 64 ? xb : 64, b);
+  for (int it = 0; it < iters; ++it) {
+    const int cur = it & 1, last = it == iters - 1;
+    ba.cur = cur;
+    SN_TIMED(kRagged ? "emd_ragged_bid" : "emd_general_bid", s,
+             (emd_general_bid_kernel<kRagged><<<bid_grid, kGThreads, 0, s>>>(ba)));
+    if (!last) emd_general_window_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, (unsigned)it + 1, w);
+    emd_general_assign_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, last, w, assignment);
+  }
+  emd_general_dist_kernel<kRagged><<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, assignment, dist,
+                                                                                r);
+  return sn::launch_status(what);
+}
+
+template <bool kRagged>
+int backward_launches(const char *what, const float *xyz1, const float *xyz2, const float *graddist,
+                      const int *assignment, int b, int n, int m, Ragged r, float *gradxyz1, float *gradxyz2,
+                      void *workspace, size_t workspace_bytes, void *stream) {
+  hipStream_t s = sn::as_stream(stream);
+  BwdWs w{};
+  if (gradxyz2) {
+    SN_REQUIRE(workspace && workspace_bytes >= bwd_bytes(b, n, m), "%s: workspace too small (%zu < %zu)", what,
+               workspace_bytes, bwd_bytes(b, n, m));
+    w = bwd_carve(workspace, b, n, m);
+    SN_HIP(hipMemsetAsync(w.count, 0, (size_t)b * m * 4, s));
+  }
+  emd_general_bwd1_kernel<kRagged><<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, graddist,
+                                                                                assignment, gradxyz1, w.count, r);
+  if (gradxyz2) {
+    emd_general_bwd_scan_kernel<<<b, kSortThreads, 0, s>>>(m, w);
+    emd_general_bwd_scatter_kernel<kRagged><<<b, kSortThreads, 0, s>>>(n, m, assignment, gradxyz1, w, r);
+    emd_general_bwd_sum_kernel<<<elt_blocks((long)b * m), kGThreads, 0, s>>>(b, n, m, w, gradxyz2);
+  }
+  return sn::launch_status(what);
+}
+
+}  // namespace
+
 extern "C" int sn_emd_forward_general(const float *xyz1, const float *xyz2, int b, int n, int m, float eps, int iters,
                                       float *dist, int *assignment, void *workspace, size_t workspace_bytes,
                                       long long *stats, void *stream) {
@@ -461,30 +564,29 @@ extern "C" int sn_emd_forward_general(const float *xyz1, const float *xyz2, int 
     if (!(e && e[0] == '1') && persistent_shape(b, n, m))
       return sn_emd_forward(xyz1, xyz2, b, n, eps, iters, dist, assignment, workspace, workspace_bytes, stats, stream);
   }
-  hipStream_t s = sn::as_stream(stream);
-  const GenWs w = carve(workspace, b, n, m);
-  gen_init_kernel<<<elt_blocks((long)b * (m > n ? m : n)), kGThreads, 0, s>>>(b, n, m, assignment, w);
-  BidArgs ba;
-  ba.B = b;
-  ba.n = n;
-  ba.m = m;
-  ba.eps = eps;
-  ba.xyz1 = xyz1;
-  ba.xyz2 = xyz2;
-  ba.w = w;
-  ba.stats = stats;
-  const dim3 bid_grid(bid_blocks(b, n), b);
-  int xb = (n + kGThreads - 1) / kGThreads;
-  const dim3 list_grid(xb < 64 ? xb : 64, b);
-  for (int it = 0; it < iters; ++it) {
-    const int cur = it & 1, last = it == iters - 1;
-    ba.cur = cur;
-    SN_TIMED("emd_general_bid", s, (emd_general_bid_kernel<<<bid_grid, kGThreads, 0, s>>>(ba)));
-    if (!last) emd_general_window_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, (unsigned)it + 1, w);
-    emd_general_assign_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, last, w, assignment);
-  }
-  emd_general_dist_kernel<<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, assignment, dist);
-  return sn::launch_status("sn_emd_forward_general");
+  return forward_launches<false>("sn_emd_forward_general", xyz1, xyz2, b, n, m, Ragged{nullptr, nullptr}, eps, iters, dist,
+                                 assignment, workspace, stats, stream);
+}
+
+// ---- ragged batches: the same launches over the padded widths; never the persistent auction
+extern "C" size_t sn_emd_ragged_workspace_bytes(int b, int n, int m) {
+  if (b < 1 || n < 1 || m < 1) return 0;
+  return carve_bytes(b, n, m);
+}
+
+extern "C" int sn_emd_forward_ragged(const float *xyz1, const float *xyz2, int b, int n, int m, const int *lengths1,
+                                     const int *lengths2, float eps, int iters, float *dist, int *assignment,
+                                     void *workspace, size_t workspace_bytes, long long *stats, void *stream) {
+  SN_REQUIRE(xyz1 && xyz2 && lengths1 && lengths2 && dist && assignment && workspace,
+             "sn_emd_forward_ragged: null pointer");
+  SN_REQUIRE(b >= 1 && b <= 65535, "sn_emd_forward_ragged: batch size must be in [1,65535] (got %d)", b);
+  SN_REQUIRE(n >= 1 && m >= 1 && n <= (1 << 20) && m <= (1 << 20),
+             "sn_emd_forward_ragged: the padded widths must be in [1, 2^20] (got n=%d, m=%d)", n, m);
+  SN_REQUIRE(iters >= 0, "sn_emd_forward_ragged: iters must be >= 0");
+  SN_REQUIRE(workspace_bytes >= carve_bytes(b, n, m), "sn_emd_forward_ragged: workspace too small (%zu < %zu)",
+             workspace_bytes, carve_bytes(b, n, m));
+  return forward_launches<true>("sn_emd_forward_ragged", xyz1, xyz2, b, n, m, Ragged{lengths1, lengths2}, eps, iters,
+                                dist, assignment, workspace, stats, stream);
 }
 
 extern "C" size_t sn_emd_general_backward_workspace_bytes(int b, int n, int m) {
@@ -498,20 +600,24 @@ extern "C" int sn_emd_backward_general(const float *xyz1, const float *xyz2, con
   SN_REQUIRE(xyz1 && xyz2 && graddist && assignment && gradxyz1, "sn_emd_backward_general: null pointer");
   SN_REQUIRE(b >= 1 && b <= 65535 && n >= 1 && n <= m && m <= (1 << 20),
              "sn_emd_backward_general: need 1 <= b <= 65535, 1 <= n <= m <= 2^20 (got b=%d, n=%d, m=%d)", b, n, m);
-  hipStream_t s = sn::as_stream(stream);
-  BwdWs w{};
-  if (gradxyz2) {
-    SN_REQUIRE(workspace && workspace_bytes >= bwd_bytes(b, n, m),
-               "sn_emd_backward_general: workspace too small (%zu < %zu)", workspace_bytes, bwd_bytes(b, n, m));
-    w = bwd_carve(workspace, b, n, m);
-    SN_HIP(hipMemsetAsync(w.count, 0, (size_t)b * m * 4, s));
-  }
-  emd_general_bwd1_kernel<<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, graddist, assignment,
-                                                                        gradxyz1, w.count);
-  if (gradxyz2) {
-    emd_general_bwd_scan_kernel<<<b, kSortThreads, 0, s>>>(m, w);
-    emd_general_bwd_scatter_kernel<<<b, kSortThreads, 0, s>>>(n, m, assignment, gradxyz1, w);
-    emd_general_bwd_sum_kernel<<<elt_blocks((long)b * m), kGThreads, 0, s>>>(b, n, m, w, gradxyz2);
-  }
-  return sn::launch_status("sn_emd_backward_general");
+  return backward_launches<false>("sn_emd_backward_general", xyz1, xyz2, graddist, assignment, b, n, m,
+                                  Ragged{nullptr, nullptr}, gradxyz1, gradxyz2, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t sn_emd_ragged_backward_workspace_bytes(int b, int n, int m) {
+  if (b < 1 || n < 1 || m < 1) return 0;
+  return bwd_bytes(b, n, m);
+}
+
+extern "C" int sn_emd_backward_ragged(const float *xyz1, const float *xyz2, const float *graddist,
+                                      const int *assignment, int b, int n, int m, const int *lengths1,
+                                      const int *lengths2, float *gradxyz1, float *gradxyz2, void *workspace,
+                                      size_t workspace_bytes, void *stream) {
+  SN_REQUIRE(xyz1 && xyz2 && graddist && assignment && lengths1 && lengths2 && gradxyz1,
+             "sn_emd_backward_ragged: null pointer");
+  SN_REQUIRE(b >= 1 && b <= 65535 && n >= 1 && m >= 1 && n <= (1 << 20) && m <= (1 << 20),
+             "sn_emd_backward_ragged: need 1 <= b <= 65535 and padded widths in [1, 2^20] (got b=%d, n=%d, m=%d)", b, n,
+             m);
+  return backward_launches<true>("sn_emd_backward_ragged", xyz1, xyz2, graddist, assignment, b, n, m,
+                                 Ragged{lengths1, lengths2}, gradxyz1, gradxyz2, workspace, workspace_bytes, stream);
 }

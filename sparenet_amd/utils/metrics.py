@@ -28,12 +28,23 @@ def f_score_from_chamfer(dist1, dist2, th=0.01):
                        torch.zeros_like(denom))
 
 
-def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, with_emd=True, emd_any_size=False):
+def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, with_emd=True, emd_any_size=False,
+                             pred_lengths=None, gt_lengths=None):
     """pred [B,N,3], gt [B,M,3] on the GPU -> dict of per-sample tensors [B]:
     'F-Score', 'ChamferDistance' (x1000, mean dist1 + mean dist2, utils/misc.py:198-201 with
     ChamferDistanceMean) and 'EMD' (x100; needs N == M, a multiple of 1024).
     emd_any_size=True computes 'EMD' with emd_general for any N and M: the smaller cloud bids for the larger one
-    (pred when N == M, the same value as the default path for N == M a multiple of 1024) and the mean runs over it."""
+    (pred when N == M, the same value as the default path for N == M a multiple of 1024) and the mean runs over it.
+    pred_lengths / gt_lengths (a list or an int tensor [B]; one may be left None = every row) make the batch ragged
+    (sparenet_amd.cuda.ragged): cloud i is its first lengths[i] rows, the rest is padding that is never read.
+    Precision and recall then count the valid rows, the means run over them: the distances are bit for bit those of a
+    call on that cloud alone, and so is 'F-Score'.  The means ('ChamferDistance', 'EMD') are float64 sums over the valid
+    rows rounded once to fp32, where the dense path takes torch's fp32 mean: the two agree to fp32 rounding, not bit
+    for bit.
+    'EMD' then needs emd_any_size=True and pred_lengths[i] <= gt_lengths[i] for every cloud (pred bids; checked when
+    the lengths are host values)."""
+    if pred_lengths is not None or gt_lengths is not None:
+        return _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths)
     dist1, dist2 = ChamferDistanceFunction.apply(pred, gt)
     out = {"F-Score": f_score_from_chamfer(dist1, dist2, th),
            "ChamferDistance": (dist1.mean(dim=1) + dist2.mean(dim=1)) * 1000}
@@ -44,6 +55,39 @@ def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, wit
     elif with_emd:
         dist, _ = emdModule()(pred, gt, emd_eps, emd_iters)
         out["EMD"] = torch.sqrt(dist).mean(dim=1) * 100
+    return out
+
+
+def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths):
+    from sparenet_amd.cuda.ragged import chamfer_ragged, device_lengths, emd_ragged, masked_mean, valid_mask
+
+    b = pred.size(0)
+    if pred_lengths is None:
+        pred_lengths = [pred.size(1)] * b
+    if gt_lengths is None:
+        gt_lengths = [gt.size(1)] * b
+    # converted (host values: range-checked and uploaded) once; every op below takes the device tensors as they are
+    l1, hp = device_lengths(pred_lengths, b, pred.size(1), pred.device, "pred_lengths")
+    l2, hg = device_lengths(gt_lengths, b, gt.size(1), gt.device, "gt_lengths")
+    if with_emd:
+        if not emd_any_size:
+            raise ValueError("fused_validation_metrics: 'EMD' of a ragged batch needs emd_any_size=True")
+        if hp is not None and hg is not None:
+            bad = [i for i, (p, g) in enumerate(zip(hp, hg)) if p > g]
+            if bad:
+                raise ValueError(f"fused_validation_metrics: 'EMD' needs pred_lengths[i] <= gt_lengths[i] (pred bids for "
+                                 f"gt); cloud {bad[0]} has {hp[bad[0]]} > {hg[bad[0]]}")
+    dist1, dist2 = chamfer_ragged(pred, gt, l1, l2)
+    th2 = float(th) * float(th)
+    m1, m2 = valid_mask(l1, pred.size(1), pred.device), valid_mask(l2, gt.size(1), gt.device)
+    precision = ((dist1 < th2) & m1).sum(dim=1).double() / l1.clamp(1, pred.size(1))
+    recall = ((dist2 < th2) & m2).sum(dim=1).double() / l2.clamp(1, gt.size(1))
+    denom = precision + recall
+    out = {"F-Score": torch.where(denom > 0, 2 * precision * recall / denom.clamp_min(1e-300), torch.zeros_like(denom)),
+           "ChamferDistance": (masked_mean(dist1, l1) + masked_mean(dist2, l2)) * 1000}
+    if with_emd:
+        dist, _ = emd_ragged(pred, gt, l1, l2, emd_eps, emd_iters)
+        out["EMD"] = masked_mean(torch.sqrt(dist), l1) * 100
     return out
 
 
