@@ -17,8 +17,11 @@
  *     failure is an error code + sn_last_error() text, and the Python mirror
  *     raises);
  *   - workspace: ops that need scratch take (workspace, workspace_bytes); the
- *     matching sn_*_workspace_bytes() says how much.  Workspace contents need
- *     no initialisation by the caller;
+ *     matching sn_*_workspace_bytes() says how much.  Each workspace is defined
+ *     by ONE layout function next to its entry point (sn::Carver in
+ *     sparenet_amd/csrc/common.hpp): the size export measures that layout, the
+ *     entry point carves it and checks workspace_bytes against it.  Workspace
+ *     contents need no initialisation by the caller;
  *   - thread safety: no global mutable state except the thread-local
  *     last-error string; safe to call concurrently from several host threads
  *     on different streams/devices (the reference is driven that way by

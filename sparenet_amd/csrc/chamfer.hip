@@ -257,6 +257,17 @@ struct BwdLists {
   int *list;   // [B, N + M]  the inverse lists: lists of cloud-1 points hold indices k of cloud 2 and vice versa
   int *longs;  // [1 + B (N + M) / 64]  count, then the global slots (b (N + M) + slot) of the lists > kLongList
 };
+// the backward's workspace; ragged batches lay the same arrays out by the padded widths
+BwdLists bwd_layout(sn::Carver &c, int b, int n, int m) {
+  const size_t arr = sn::align_up((size_t)b * ((size_t)n + m) * 4, 256);
+  BwdLists L;
+  L.cnt = c.take<int>(arr);
+  L.off = c.take<int>(arr);
+  L.fill = c.take<int>(arr);
+  L.list = c.take<int>(arr);
+  L.longs = c.take256<int>(arr / 64 + 256);
+  return L;
+}
 
 // The backward kernels serve dense and ragged batches.  kRagged = false: every row is a point, n1 = N and n2 = M, the
 // code of sn_chamfer_backward as it always was.  kRagged = true (sn_chamfer_backward_ragged): N and M are the padded
@@ -630,8 +641,7 @@ extern "C" int sn_chamfer_forward_ragged(const float *xyz1, const float *xyz2, i
 
 extern "C" size_t sn_chamfer_backward_workspace_bytes(int b, int n, int m) {
   if (b < 1 || n < 1 || m < 1) return 0;
-  const size_t arr = sn::align_up((size_t)b * ((size_t)n + m) * 4, 256);
-  return 4 * arr + sn::align_up(arr / 64 + 256, 256);  // cnt, off, fill, list + the directory of the long lists
+  return sn::layout_bytes(bwd_layout, b, n, m);
 }
 
 extern "C" size_t sn_chamfer_backward_ragged_workspace_bytes(int b, int n, int m) {
@@ -651,17 +661,10 @@ int chamfer_backward(const char *what, const float *xyz1, const float *xyz2, con
              "%s: null pointer", what);
   SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "%s: need b,n,m >= 1", what);
   SN_REQUIRE((long)b * ((long)n + m) < (1L << 30), "%s: too large", what);
-  SN_REQUIRE(workspace_bytes >= sn_chamfer_backward_workspace_bytes(b, n, m),
-             "%s: workspace too small (%zu < %zu)", what, workspace_bytes,
-             sn_chamfer_backward_workspace_bytes(b, n, m));
-  const size_t arr = sn::align_up((size_t)b * ((size_t)n + m) * 4, 256);
-  char *p = static_cast<char *>(workspace);
-  BwdLists L;
-  L.cnt = reinterpret_cast<int *>(p);
-  L.off = reinterpret_cast<int *>(p + arr);
-  L.fill = reinterpret_cast<int *>(p + 2 * arr);
-  L.list = reinterpret_cast<int *>(p + 3 * arr);
-  L.longs = reinterpret_cast<int *>(p + 4 * arr);
+  sn::Carver carver(workspace);
+  const BwdLists L = bwd_layout(carver, b, n, m);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace too small (%zu < %zu)", what, workspace_bytes,
+             carver.bytes());
   const long total = (long)b * n + (long)b * m;
   long blocks = (total + 255) / 256;
   if (blocks > 2048) blocks = 2048;

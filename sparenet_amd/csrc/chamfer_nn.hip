@@ -301,43 +301,34 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
   }
 }
 
-struct SideBytes {
-  size_t perm, hist, bbox, sorted4, mstream, sbbox, total;
-};
-SideBytes side_bytes(int b, int n) {
-  const size_t nsb = (size_t)sn::ceil_div(n, 64);
-  SideBytes s;
-  s.perm = sn::align_up((size_t)b * n * 4, 256);
-  s.hist = (size_t)b * kSortCells * 4;
-  s.bbox = sn::align_up((size_t)b * 24, 256);
-  s.sorted4 = (size_t)b * nsb * 64 * 16;
-  s.mstream = (size_t)b * nsb * 64 * 16;
-  s.sbbox = (size_t)b * nsb * 32;
-  s.total = s.perm + s.hist + s.bbox + s.sorted4 + s.mstream + s.sbbox;
-  return s;
-}
-
-NnSide carve_side(char *&p, const float *xyz, int b, int n) {
-  const SideBytes sz = side_bytes(b, n);
+// the workspace: both sides' arrays, then the two sort-scratch arrays
+NnSide side_layout(sn::Carver &c, int b, int n) {
   NnSide s;
-  s.xyz = xyz;
+  s.xyz = nullptr;  // the entry point's
   s.n = n;
   s.nsb = sn::ceil_div(n, 64);
-  s.perm = reinterpret_cast<int *>(p); p += sz.perm;
-  s.hist = reinterpret_cast<int *>(p); p += sz.hist;
-  s.bbox = reinterpret_cast<float *>(p); p += sz.bbox;
-  s.sorted4 = reinterpret_cast<f4 *>(p); p += sz.sorted4;
-  s.mstream = reinterpret_cast<f4 *>(p); p += sz.mstream;
-  s.sbbox = reinterpret_cast<float *>(p); p += sz.sbbox;
+  s.perm = c.take256<int>((size_t)b * n * 4);
+  s.hist = c.take<int>((size_t)b * kSortCells * 4);
+  s.bbox = c.take256<float>((size_t)b * 24);
+  s.sorted4 = c.take<f4>((size_t)b * s.nsb * 64 * 16);
+  s.mstream = c.take<f4>((size_t)b * s.nsb * 64 * 16);
+  s.sbbox = c.take<float>((size_t)b * s.nsb * 32);
   return s;
+}
+struct NnWs {
+  NnSide s1, s2;
+  int *cell_of, *cell_of2;  // sort scratch of cloud 1 and of cloud 2
+};
+NnWs nn_layout(sn::Carver &c, int b, int n, int m) {
+  const size_t scratch = (size_t)b * (n > m ? n : m) * 4;
+  return {side_layout(c, b, n), side_layout(c, b, m), c.take256<int>(scratch), c.take256<int>(scratch)};
 }
 
 }  // namespace
 
 extern "C" size_t sn_chamfer_workspace_bytes(int b, int n, int m) {
   if (b < 1 || n < 1 || m < 1) return 0;
-  const int big = n > m ? n : m;
-  return side_bytes(b, n).total + side_bytes(b, m).total + 2 * sn::align_up((size_t)b * big * 4, 256);
+  return sn::layout_bytes(nn_layout, b, n, m);
 }
 
 extern "C" int sn_chamfer_forward_sorted(const float *xyz1, const float *xyz2, int b, int n, int m,
@@ -348,18 +339,18 @@ extern "C" int sn_chamfer_forward_sorted(const float *xyz1, const float *xyz2, i
   SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "sn_chamfer_forward_sorted: need b,n,m >= 1 (got %d,%d,%d)", b, n, m);
   SN_REQUIRE((long)b * n < (1L << 26) && (long)b * m < (1L << 26) && n < (1 << 26) && m < (1 << 26),
              "sn_chamfer_forward_sorted: too large");
-  SN_REQUIRE(workspace_bytes >= sn_chamfer_workspace_bytes(b, n, m),
-             "sn_chamfer_forward_sorted: workspace too small (%zu < %zu)", workspace_bytes,
-             sn_chamfer_workspace_bytes(b, n, m));
+  sn::Carver carver(workspace);
+  const NnWs w = nn_layout(carver, b, n, m);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_chamfer_forward_sorted: workspace too small (%zu < %zu)",
+             workspace_bytes, carver.bytes());
   hipStream_t s = sn::as_stream(stream);
   SN_REFUSE_CAPTURE(s, "sn_chamfer_forward_sorted");
-  char *p = static_cast<char *>(workspace);
-  NnSide s1 = carve_side(p, xyz1, b, n), s2 = carve_side(p, xyz2, b, m);
-  int *cell_of = reinterpret_cast<int *>(p);  // sort scratch of cloud 1; cloud 2's follows it
-  int *cell_of2 = reinterpret_cast<int *>(p + sn::align_up((size_t)b * (n > m ? n : m) * 4, 256));
+  NnSide s1 = w.s1, s2 = w.s2;
+  s1.xyz = xyz1;
+  s2.xyz = xyz2;
   if (sn::prof_enabled()) sn::prof_begin("chamfer_fwd", s);
-  SN_REQUIRE(cloud_sort_pair(b, SortSide{s1.n, s1.xyz, s1.bbox, s1.hist, cell_of, s1.perm},
-                             SortSide{s2.n, s2.xyz, s2.bbox, s2.hist, cell_of2, s2.perm}, s) == 0,
+  SN_REQUIRE(cloud_sort_pair(b, SortSide{s1.n, s1.xyz, s1.bbox, s1.hist, w.cell_of, s1.perm},
+                             SortSide{s2.n, s2.xyz, s2.bbox, s2.hist, w.cell_of2, s2.perm}, s) == 0,
              "sn_chamfer_forward_sorted: cannot size the sort kernel's LDS");
   for (NnSide *side : {&s1, &s2}) {
     const long sbs = (long)b * side->nsb;

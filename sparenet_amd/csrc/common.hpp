@@ -150,4 +150,33 @@ inline bool knobs_per_call() {
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// A workspace is described ONCE, by a layout function that takes its arrays from a Carver in order and returns the
+// struct of pointers.  On the caller's base pointer that carves the workspace; on a null base it only measures
+// (every pointer comes back null), which is what the sn_*_workspace_bytes exports and the "workspace too small" checks
+// read through bytes().  A step that is taken and not kept is counted and not carved.
+class Carver {
+ public:
+  explicit Carver(void *base) : base_(static_cast<char *>(base)) {}
+  template <class T>
+  T *take(size_t bytes) {  // the next `bytes` bytes
+    T *p = base_ ? reinterpret_cast<T *>(base_ + off_) : nullptr;
+    off_ += bytes;
+    return p;
+  }
+  template <class T>
+  T *take256(size_t bytes) { return take<T>(align_up(bytes, 256)); }  // the step rounded up to 256
+  size_t bytes() const { return off_; }
+
+ private:
+  char *base_;
+  size_t off_ = 0;
+};
+// what a layout function asks for: layout(carver, shape...) on a measuring carver
+template <class Layout, class... Shape>
+size_t layout_bytes(Layout layout, Shape... shape) {
+  Carver c(nullptr);
+  layout(c, shape...);
+  return c.bytes();
+}
+
 }  // namespace sn

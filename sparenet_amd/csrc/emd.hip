@@ -1987,39 +1987,45 @@ constexpr size_t kDiagWords = 16 + 64 * 64;                        // int64 phas
 constexpr size_t kCtlWords = 32 + 2 * 32 * 1024;                    // ticket, abort, up to 1024 team counters + 1024 note blocks
 constexpr size_t kCtlBytes = 4 * kCtlWords + 8 * kDiagWords;
 
-EmdWs carve(void *workspace, int b, int n) {
-  char *p = static_cast<char *>(workspace);
-  const size_t arr = sn::align_up((size_t)b * n * 4, 256);
-  const size_t arr2 = sn::align_up((size_t)b * n * 8, 256);
+// the persistent auction's arrays, in front of the control block (common.hpp, Carver)
+EmdWs arrays_layout(sn::Carver &c, int b, int n) {
+  const size_t bn = (size_t)b * n;
   EmdWs ws;
-  ws.assignment_inv = reinterpret_cast<int *>(p); p += arr;
-  ws.price = reinterpret_cast<float *>(p); p += arr;
-  ws.bid = reinterpret_cast<int *>(p); p += arr;
-  ws.bid2 = reinterpret_cast<int *>(p); p += arr;
-  ws.rec = reinterpret_cast<int *>(p); p += sn::align_up((size_t)b * n * 16, 256);
-  ws.max_inc = reinterpret_cast<float *>(p); p += arr;
-  ws.max_idx = reinterpret_cast<int *>(p); p += arr;
-  ws.head = reinterpret_cast<int *>(p); p += arr;
-  ws.list[0] = reinterpret_cast<int *>(p); p += arr2;
-  ws.prt = reinterpret_cast<float *>(p); p += arr;
-  ws.bins[0] = reinterpret_cast<int *>(p); p += sn::align_up((size_t)b * kRankBins * 4, 256);
-  ws.bins[1] = reinterpret_cast<int *>(p); p += sn::align_up((size_t)b * kRankBins * 4, 256);
-  ws.t4s = reinterpret_cast<f4 *>(p); p += sn::align_up((size_t)b * n * 16, 256);
-  ws.pk = reinterpret_cast<float2 *>(p); p += arr2;
-  ws.rank2 = reinterpret_cast<int *>(p); p += arr;
-  ws.mstream = reinterpret_cast<f4 *>(p); p += sn::align_up((size_t)b * n * 16, 256);
-  ws.tperm = reinterpret_cast<int *>(p); p += arr;
-  ws.cell_of = reinterpret_cast<int *>(p); p += arr;
-  ws.hist = reinterpret_cast<int *>(p); p += (size_t)b * kSortCells * 4;
-  ws.bbox = reinterpret_cast<float *>(p); p += sn::align_up((size_t)b * 24, 256);
-  ws.sbbox = reinterpret_cast<float *>(p); p += sn::align_up((size_t)b * (n / 16) * 32, 256);
-  ws.perm1 = reinterpret_cast<int *>(p); p += arr;
-  ws.rank1 = reinterpret_cast<int *>(p); p += arr;
-  ws.flags = reinterpret_cast<int *>(p); p += arr;
-  ws.hist1 = reinterpret_cast<int *>(p); p += (size_t)b * kSortCells * 4;
-  ws.bbox1 = reinterpret_cast<float *>(p); p += sn::align_up((size_t)b * 24, 256);
-  ws.far = reinterpret_cast<int *>(p); p += sn::align_up((size_t)b * 4, 256);
-  ws.ctl = p; p += kCtlBytes;
+  ws.assignment_inv = c.take256<int>(bn * 4);
+  ws.price = c.take256<float>(bn * 4);
+  ws.bid = c.take256<int>(bn * 4);
+  ws.bid2 = c.take256<int>(bn * 4);
+  ws.rec = c.take256<int>(bn * 16);
+  ws.max_inc = c.take256<float>(bn * 4);
+  ws.max_idx = c.take256<int>(bn * 4);
+  ws.head = c.take256<int>(bn * 4);
+  ws.list[0] = c.take256<int>(bn * 8);
+  ws.prt = c.take256<float>(bn * 4);
+  ws.bins[0] = c.take256<int>((size_t)b * kRankBins * 4);
+  ws.bins[1] = c.take256<int>((size_t)b * kRankBins * 4);
+  ws.t4s = c.take256<f4>(bn * 16);
+  ws.pk = c.take256<float2>(bn * 8);
+  ws.rank2 = c.take256<int>(bn * 4);
+  ws.mstream = c.take256<f4>(bn * 16);
+  ws.tperm = c.take256<int>(bn * 4);
+  ws.cell_of = c.take256<int>(bn * 4);
+  ws.hist = c.take<int>((size_t)b * kSortCells * 4);
+  ws.bbox = c.take256<float>((size_t)b * 24);
+  ws.sbbox = c.take256<float>((size_t)b * (n / 16) * 32);
+  ws.perm1 = c.take256<int>(bn * 4);
+  ws.rank1 = c.take256<int>(bn * 4);
+  ws.flags = c.take256<int>(bn * 4);
+  ws.hist1 = c.take<int>((size_t)b * kSortCells * 4);
+  ws.bbox1 = c.take256<float>((size_t)b * 24);
+  ws.far = c.take256<int>((size_t)b * 4);
+  ws.ctl = nullptr;
+  return ws;
+}
+
+// the whole workspace: the arrays, then the control block
+EmdWs layout(sn::Carver &c, int b, int n) {
+  EmdWs ws = arrays_layout(c, b, n);
+  ws.ctl = c.take<char>(kCtlBytes);  // kCtlWords control words, then the kDiagWords diagnostic words
   return ws;
 }
 
@@ -2259,15 +2265,13 @@ extern "C" long long sn_emd_prof_exec(double *total_ms, int reset) {
 
 extern "C" size_t sn_emd_workspace_bytes(int b, int n) {
   if (b < 1 || n < 1) return 0;
-  return 14 * sn::align_up((size_t)b * n * 4, 256) + 2 * sn::align_up((size_t)b * n * 8, 256) +
-         2 * sn::align_up((size_t)b * kRankBins * 4, 256) + 3 * sn::align_up((size_t)b * n * 16, 256) +
-         2 * (size_t)b * kSortCells * 4 + 2 * sn::align_up((size_t)b * 24, 256) +
-         sn::align_up((size_t)b * (n / 16) * 32, 256) + sn::align_up((size_t)b * 4, 256) + kCtlBytes;
+  return sn::layout_bytes(layout, b, n);
 }
 
-// byte offset of the diagnostic words (SN_EMD_DIAG) inside the workspace
+// byte offset of the diagnostic words (SN_EMD_DIAG) inside the workspace: behind the control words
 extern "C" size_t sn_emd_diag_offset(int b, int n) {
-  return sn_emd_workspace_bytes(b, n) - 8 * kDiagWords;
+  if (b < 1 || n < 1) return 0;
+  return sn::layout_bytes(arrays_layout, b, n) + 4 * kCtlWords;
 }
 
 // 0: the fence-free / XCD-local paths are in use on the current device; 2: the library fell back to fenced
@@ -2312,9 +2316,10 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
   SN_REQUIRE(n >= 1024 && n % 1024 == 0 && n <= (1 << 20),
              "sn_emd_forward: n must be a multiple of 1024, <= 2^20 (got %d)", n);
   SN_REQUIRE(iters >= 0, "sn_emd_forward: iters must be >= 0");
-  SN_REQUIRE(workspace_bytes >= sn_emd_workspace_bytes(b, n),
-             "sn_emd_forward: workspace too small (%zu < %zu)", workspace_bytes,
-             sn_emd_workspace_bytes(b, n));
+  sn::Carver carver(workspace);
+  const EmdWs ws = layout(carver, b, n);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_emd_forward: workspace too small (%zu < %zu)", workspace_bytes,
+             carver.bytes());
   hipStream_t s = sn::as_stream(stream);
   SN_REFUSE_CAPTURE(s, "sn_emd_forward");
   int dev = 0, cus = 0;
@@ -2346,7 +2351,6 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
     }
     if (st.verified != 1) safe = 1;   // unverified (yet) or failed: the conservative path
   }
-  const EmdWs ws = carve(workspace, b, n);
   const long total = (long)b * n;
   const int eblocks = (int)((total + kThreads - 1) / kThreads < 2048 ? (total + kThreads - 1) / kThreads : 2048);
   // both clouds' Hilbert sorts in one launch; the bidders' cell ids go to `flags` for the moment (every word of it

@@ -72,25 +72,20 @@ int bid_blocks(int B, int n) {
   return (int)((lanes + kGThreads - 1) / kGThreads);
 }
 
-size_t carve_bytes(int b, int n, int m) {
-  const size_t tm = sn::align_up((size_t)b * m * 4, 256), tn = sn::align_up((size_t)b * n * 4, 256);
-  return 5 * tm + 4 * tn + 2 * sn::align_up((size_t)b * 4, 256);  // max_idx counts twice (8-byte words)
-}
-
-GenWs carve(void *workspace, int b, int n, int m) {
-  char *p = static_cast<char *>(workspace);
-  const size_t tm = sn::align_up((size_t)b * m * 4, 256), tn = sn::align_up((size_t)b * n * 4, 256);
+// the workspace of the stream-ordered auction
+GenWs gen_layout(sn::Carver &c, int b, int n, int m) {
+  const size_t tm = (size_t)b * m * 4, tn = (size_t)b * n * 4;
   GenWs w;
-  w.max_idx = reinterpret_cast<unsigned long long *>(p); p += 2 * tm;
-  w.price = reinterpret_cast<float *>(p); p += tm;
-  w.assign_inv = reinterpret_cast<int *>(p); p += tm;
-  w.max_key = reinterpret_cast<unsigned *>(p); p += tm;
-  w.bid = reinterpret_cast<int *>(p); p += tn;
-  w.bid_inc = reinterpret_cast<float *>(p); p += tn;
-  w.list[0] = reinterpret_cast<int *>(p); p += tn;
-  w.list[1] = reinterpret_cast<int *>(p); p += tn;
-  w.cnt[0] = reinterpret_cast<int *>(p); p += sn::align_up((size_t)b * 4, 256);
-  w.cnt[1] = reinterpret_cast<int *>(p);
+  w.max_idx = c.take<unsigned long long>(2 * sn::align_up(tm, 256));  // 8-byte words: two word arrays
+  w.price = c.take256<float>(tm);
+  w.assign_inv = c.take256<int>(tm);
+  w.max_key = c.take256<unsigned>(tm);
+  w.bid = c.take256<int>(tn);
+  w.bid_inc = c.take256<float>(tn);
+  w.list[0] = c.take256<int>(tn);
+  w.list[1] = c.take256<int>(tn);
+  w.cnt[0] = c.take256<int>((size_t)b * 4);
+  w.cnt[1] = c.take256<int>((size_t)b * 4);
   return w;
 }
 
@@ -321,18 +316,12 @@ struct BwdWs {
   float *terms; // [b, n, 3] gradxyz1 rows in (target, j) order
 };
 
-size_t bwd_bytes(int b, int n, int m) {
-  return 3 * sn::align_up((size_t)b * m * 4, 256) + sn::align_up((size_t)b * n * 12, 256);
-}
-
-BwdWs bwd_carve(void *workspace, int b, int n, int m) {
-  char *p = static_cast<char *>(workspace);
-  const size_t tm = sn::align_up((size_t)b * m * 4, 256);
+BwdWs bwd_layout(sn::Carver &c, int b, int n, int m) {
   BwdWs w;
-  w.count = reinterpret_cast<int *>(p); p += tm;
-  w.off = reinterpret_cast<int *>(p); p += tm;
-  w.run = reinterpret_cast<int *>(p); p += tm;
-  w.terms = reinterpret_cast<float *>(p);
+  w.count = c.take256<int>((size_t)b * m * 4);
+  w.off = c.take256<int>((size_t)b * m * 4);
+  w.run = c.take256<int>((size_t)b * m * 4);
+  w.terms = c.take256<float>((size_t)b * n * 12);
   return w;
 }
 
@@ -482,7 +471,7 @@ bool persistent_shape(int b, int n, int m) { return n == m && n % 1024 == 0 && b
 
 extern "C" size_t sn_emd_general_workspace_bytes(int b, int n, int m) {
   if (b < 1 || n < 1 || m < n) return 0;
-  const size_t own = carve_bytes(b, n, m);
+  const size_t own = sn::layout_bytes(gen_layout, b, n, m);
   if (!persistent_shape(b, n, m)) return own;
   const size_t pers = sn_emd_workspace_bytes(b, n);  // the dispatch may hand the call to sn_emd_forward
   return pers > own ? pers : own;
@@ -493,9 +482,13 @@ namespace {
 // the stream-ordered auction: three launches per iteration, no workgroup waits for another
 template <bool kRagged>
 int forward_launches(const char *what, const float *xyz1, const float *xyz2, int b, int n, int m, Ragged r, float eps,
-                     int iters, float *dist, int *assignment, void *workspace, long long *stats, void *stream) {
+                     int iters, float *dist, int *assignment, void *workspace, size_t workspace_bytes, long long *stats,
+                     void *stream) {
   hipStream_t s = sn::as_stream(stream);
-  const GenWs w = carve(workspace, b, n, m);
+  sn::Carver carver(workspace);
+  const GenWs w = gen_layout(carver, b, n, m);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace too small (%zu < %zu)", what, workspace_bytes,
+             carver.bytes());
   gen_init_kernel<kRagged><<<elt_blocks((long)b * (m > n ? m : n)), kGThreads, 0, s>>>(b, n, m, assignment, w, r);
   BidArgs ba;
   ba.B = b;
@@ -530,9 +523,10 @@ int backward_launches(const char *what, const float *xyz1, const float *xyz2, co
   hipStream_t s = sn::as_stream(stream);
   BwdWs w{};
   if (gradxyz2) {
-    SN_REQUIRE(workspace && workspace_bytes >= bwd_bytes(b, n, m), "%s: workspace too small (%zu < %zu)", what,
-               workspace_bytes, bwd_bytes(b, n, m));
-    w = bwd_carve(workspace, b, n, m);
+    sn::Carver carver(workspace);
+    w = bwd_layout(carver, b, n, m);
+    SN_REQUIRE(workspace && workspace_bytes >= carver.bytes(), "%s: workspace too small (%zu < %zu)", what,
+               workspace_bytes, carver.bytes());
     SN_HIP(hipMemsetAsync(w.count, 0, (size_t)b * m * 4, s));
   }
   emd_general_bwd1_kernel<kRagged><<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, graddist,
@@ -556,6 +550,7 @@ extern "C" int sn_emd_forward_general(const float *xyz1, const float *xyz2, int 
   SN_REQUIRE(n <= m, "sn_emd_forward_general: n=%d > m=%d: pass the smaller cloud first (xyz1 bids for xyz2)", n, m);
   SN_REQUIRE(m <= (1 << 20), "sn_emd_forward_general: m must be <= 2^20 (got %d)", m);
   SN_REQUIRE(iters >= 0, "sn_emd_forward_general: iters must be >= 0");
+  // the larger of the two layouts, whichever auction runs; each then checks its own carver
   SN_REQUIRE(workspace_bytes >= sn_emd_general_workspace_bytes(b, n, m),
              "sn_emd_forward_general: workspace too small (%zu < %zu)", workspace_bytes,
              sn_emd_general_workspace_bytes(b, n, m));
@@ -565,13 +560,13 @@ extern "C" int sn_emd_forward_general(const float *xyz1, const float *xyz2, int 
       return sn_emd_forward(xyz1, xyz2, b, n, eps, iters, dist, assignment, workspace, workspace_bytes, stats, stream);
   }
   return forward_launches<false>("sn_emd_forward_general", xyz1, xyz2, b, n, m, Ragged{nullptr, nullptr}, eps, iters, dist,
-                                 assignment, workspace, stats, stream);
+                                 assignment, workspace, workspace_bytes, stats, stream);
 }
 
 // ---- ragged batches: the same launches over the padded widths; never the persistent auction
 extern "C" size_t sn_emd_ragged_workspace_bytes(int b, int n, int m) {
   if (b < 1 || n < 1 || m < 1) return 0;
-  return carve_bytes(b, n, m);
+  return sn::layout_bytes(gen_layout, b, n, m);
 }
 
 extern "C" int sn_emd_forward_ragged(const float *xyz1, const float *xyz2, int b, int n, int m, const int *lengths1,
@@ -583,15 +578,13 @@ extern "C" int sn_emd_forward_ragged(const float *xyz1, const float *xyz2, int b
   SN_REQUIRE(n >= 1 && m >= 1 && n <= (1 << 20) && m <= (1 << 20),
              "sn_emd_forward_ragged: the padded widths must be in [1, 2^20] (got n=%d, m=%d)", n, m);
   SN_REQUIRE(iters >= 0, "sn_emd_forward_ragged: iters must be >= 0");
-  SN_REQUIRE(workspace_bytes >= carve_bytes(b, n, m), "sn_emd_forward_ragged: workspace too small (%zu < %zu)",
-             workspace_bytes, carve_bytes(b, n, m));
   return forward_launches<true>("sn_emd_forward_ragged", xyz1, xyz2, b, n, m, Ragged{lengths1, lengths2}, eps, iters,
-                                dist, assignment, workspace, stats, stream);
+                                dist, assignment, workspace, workspace_bytes, stats, stream);
 }
 
 extern "C" size_t sn_emd_general_backward_workspace_bytes(int b, int n, int m) {
   if (b < 1 || n < 1 || m < n) return 0;
-  return bwd_bytes(b, n, m);
+  return sn::layout_bytes(bwd_layout, b, n, m);
 }
 
 extern "C" int sn_emd_backward_general(const float *xyz1, const float *xyz2, const float *graddist,
@@ -606,7 +599,7 @@ extern "C" int sn_emd_backward_general(const float *xyz1, const float *xyz2, con
 
 extern "C" size_t sn_emd_ragged_backward_workspace_bytes(int b, int n, int m) {
   if (b < 1 || n < 1 || m < 1) return 0;
-  return bwd_bytes(b, n, m);
+  return sn::layout_bytes(bwd_layout, b, n, m);
 }
 
 extern "C" int sn_emd_backward_ragged(const float *xyz1, const float *xyz2, const float *graddist,

@@ -289,11 +289,16 @@ __global__ __launch_bounds__(256) void expansion_bwd_kernel(
   }
 }
 
+// the workspace: the mean MST edge length of every patch
+float *patch_mean_layout(sn::Carver &c, int b, int n, int primitive_size) {
+  return c.take256<float>((size_t)b * (n / primitive_size) * 4);
+}
+
 }  // namespace
 
 extern "C" size_t sn_expansion_workspace_bytes(int b, int n, int primitive_size) {
   if (b < 1 || n < 1 || primitive_size < 1) return 0;
-  return sn::align_up((size_t)b * (n / primitive_size) * 4, 256);
+  return sn::layout_bytes(patch_mean_layout, b, n, primitive_size);
 }
 
 extern "C" int sn_expansion_forward(const float *xyz, int b, int n, int primitive_size,
@@ -308,10 +313,10 @@ extern "C" int sn_expansion_forward(const float *xyz, int b, int n, int primitiv
              "sn_expansion_forward: primitive_size must be a power of two in [2,512] (got %d)", P);
   SN_REQUIRE(n % P == 0, "sn_expansion_forward: n (%d) must be a multiple of primitive_size (%d)", n, P);
   SN_REQUIRE(b <= 65535, "sn_expansion_forward: batch too large");
-  SN_REQUIRE(workspace_bytes >= sn_expansion_workspace_bytes(b, n, P),
-             "sn_expansion_forward: workspace too small");
+  sn::Carver carver(workspace);
+  float *patch_mean = patch_mean_layout(carver, b, n, P);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_expansion_forward: workspace too small");
   hipStream_t s = sn::as_stream(stream);
-  float *patch_mean = static_cast<float *>(workspace);
   const dim3 grid(n / P, b);
   if (sn::prof_enabled()) sn::prof_begin("expansion_fwd", s);
   switch (P <= 64 ? 1 : P / 64) {

@@ -210,9 +210,22 @@ extern "C" int sn_graph_feature_forward(const float *x, const long long *idx, in
   return sn::launch_status("sn_graph_feature_forward");
 }
 
+namespace {
+
+// the backward's workspace
+struct EdgeWs {
+  int *offs;   // [b, n] edges arriving at each point, then their starts
+  int *elist;  // [b, n, k] the edges grouped by the point they arrive at
+};
+EdgeWs edge_layout(sn::Carver &c, int b, int n, int k) {
+  return {c.take256<int>((size_t)b * n * 4), c.take<int>((size_t)b * n * k * 4)};
+}
+
+}  // namespace
+
 extern "C" size_t sn_graph_feature_backward_workspace_bytes(int b, int n, int k) {
   if (b < 1 || n < 1 || k < 1) return 0;
-  return sn::align_up((size_t)b * n * 4, 256) + (size_t)b * n * k * 4;
+  return sn::layout_bytes(edge_layout, b, n, k);
 }
 
 extern "C" int sn_graph_feature_backward(const float *grad_out, const long long *idx, int b, int c,
@@ -220,17 +233,16 @@ extern "C" int sn_graph_feature_backward(const float *grad_out, const long long 
                                          size_t workspace_bytes, void *stream) {
   SN_REQUIRE(grad_out && idx && grad_x && workspace, "sn_graph_feature_backward: null pointer");
   SN_REQUIRE(b >= 1 && c >= 1 && n >= 1 && k >= 1, "sn_graph_feature_backward: bad sizes");
-  SN_REQUIRE(workspace_bytes >= sn_graph_feature_backward_workspace_bytes(b, n, k),
-             "sn_graph_feature_backward: workspace too small");
+  sn::Carver carver(workspace);
+  const EdgeWs w = edge_layout(carver, b, n, k);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_graph_feature_backward: workspace too small");
   hipStream_t s = sn::as_stream(stream);
-  int *offs = static_cast<int *>(workspace);
-  int *elist = reinterpret_cast<int *>(static_cast<char *>(workspace) + sn::align_up((size_t)b * n * 4, 256));
   const long edges = (long)b * n * k;
-  SN_HIP(hipMemsetAsync(offs, 0, (size_t)b * n * 4, s));
-  graph_count_kernel<<<blocks_for(edges), 256, 0, s>>>(idx, n, k, edges, offs);
-  graph_scan_kernel<<<b, 1024, 0, s>>>(offs, n);
-  graph_fill_kernel<<<blocks_for(edges), 256, 0, s>>>(idx, n, k, edges, offs, elist);
+  SN_HIP(hipMemsetAsync(w.offs, 0, (size_t)b * n * 4, s));
+  graph_count_kernel<<<blocks_for(edges), 256, 0, s>>>(idx, n, k, edges, w.offs);
+  graph_scan_kernel<<<b, 1024, 0, s>>>(w.offs, n);
+  graph_fill_kernel<<<blocks_for(edges), 256, 0, s>>>(idx, n, k, edges, w.offs, w.elist);
   const long total = (long)b * c * n;
-  graph_feature_bwd_kernel<<<blocks_for(total), 256, 0, s>>>(grad_out, offs, elist, c, n, k, total, grad_x);
+  graph_feature_bwd_kernel<<<blocks_for(total), 256, 0, s>>>(grad_out, w.offs, w.elist, c, n, k, total, grad_x);
   return sn::launch_status("sn_graph_feature_backward");
 }

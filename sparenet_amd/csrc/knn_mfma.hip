@@ -265,11 +265,14 @@ int launch_knn(const float *x, const float *xx, int b, int c, int n, int k, long
   return sn::launch_status("sn_knn");
 }
 
+// the workspace: the points' squared norms
+float *sqnorm_layout(sn::Carver &c, int b, int n) { return c.take256<float>((size_t)b * n * 4); }
+
 }  // namespace
 
 extern "C" size_t sn_knn_workspace_bytes(int b, int n) {
   if (b < 1 || n < 1) return 0;
-  return sn::align_up((size_t)b * n * 4, 256);
+  return sn::layout_bytes(sqnorm_layout, b, n);
 }
 
 extern "C" int sn_knn(const float *x, int b, int c, int n, int k, long long *idx, void *workspace,
@@ -278,9 +281,10 @@ extern "C" int sn_knn(const float *x, int b, int c, int n, int k, long long *idx
   SN_REQUIRE(b >= 1 && c >= 1 && n >= 1, "sn_knn: need b, c, n >= 1");
   SN_REQUIRE(k >= 1 && k <= 20 && k <= n, "sn_knn: need 1 <= k <= min(n, 20) (got %d)", k);
   SN_REQUIRE(b <= 65535, "sn_knn: batch too large");
-  SN_REQUIRE(workspace_bytes >= sn_knn_workspace_bytes(b, n), "sn_knn: workspace too small");
+  sn::Carver carver(workspace);
+  float *xx = sqnorm_layout(carver, b, n);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_knn: workspace too small");
   hipStream_t s = sn::as_stream(stream);
-  float *xx = static_cast<float *>(workspace);
   const long total = (long)b * n;
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   knn_sqnorm_kernel<<<blocks, 256, 0, s>>>(x, c, n, total, xx);

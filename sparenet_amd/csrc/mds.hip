@@ -1039,14 +1039,35 @@ static bool mds_use_clustered(int n) {
 
 constexpr size_t kMdsTeamCtlBytes = 128 + 128 * 3 * 1024;  // header + exchange lines of up to 1024 team members
 
+namespace {
+
+struct MdsClusteredWs {  // the clustered kernel's workspace
+  int *perm;         // [b, n] sorted position -> point
+  int *cell_of;      // [b, n] sort scratch
+  int *hist;         // [b, 4096] cell offsets
+  float *bbox;       // [b, 6] in 256-byte slots
+  MdsTeamCtl *tctl;  // the dense-regime teams' control block
+};
+MdsClusteredWs clustered_layout(sn::Carver &c, int b, int n) {
+  MdsClusteredWs w;
+  w.perm = c.take256<int>((size_t)b * n * 4);
+  w.cell_of = c.take256<int>((size_t)b * n * 4);
+  w.hist = c.take<int>((size_t)b * kSortCells * 4);
+  w.bbox = c.take256<float>(256 * (size_t)b);
+  w.tctl = c.take<MdsTeamCtl>(kMdsTeamCtlBytes);
+  return w;
+}
+// the generic kernel's: one word per point
+float *generic_layout(sn::Carver &c, int b, int n) { return c.take<float>((size_t)b * n * 4); }
+
+}  // namespace
+
 extern "C" size_t sn_mds_workspace_bytes(int b, int n) {
   if (b < 1 || n < 1) return 0;
-  if (mds_use_clustered(n))  // perm + cell ids + cell offsets + bounding boxes + the dense-regime teams' control block
-    return sn::align_up((size_t)b * n * 4, 256) * 2 + (size_t)b * kSortCells * 4 + sn::align_up(256 * (size_t)b, 256) +
-           kMdsTeamCtlBytes;
+  if (mds_use_clustered(n)) return sn::layout_bytes(clustered_layout, b, n);
   int bs = 1;
   while (bs * 2 <= n && bs < 1024) bs *= 2;
-  return (n + bs - 1) / bs <= 24 ? 0 : (size_t)b * n * 4;
+  return (n + bs - 1) / bs <= 24 ? 0 : sn::layout_bytes(generic_layout, b, n);
 }
 
 extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_mst_length,
@@ -1064,15 +1085,12 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
   hipStream_t s = sn::as_stream(stream);
   if (sn::prof_enabled()) sn::prof_begin("mds", s);
   if (mds_use_clustered(n)) {
-    SN_REQUIRE(workspace && workspace_bytes >= sn_mds_workspace_bytes(b, n),
-               "sn_mds: workspace too small (%zu < %zu)", workspace_bytes, sn_mds_workspace_bytes(b, n));
-    char *w = static_cast<char *>(workspace);
-    int *perm = reinterpret_cast<int *>(w); w += sn::align_up((size_t)b * n * 4, 256);
-    int *cell_of = reinterpret_cast<int *>(w); w += sn::align_up((size_t)b * n * 4, 256);
-    int *hist = reinterpret_cast<int *>(w); w += (size_t)b * kSortCells * 4;
-    float *bbox = reinterpret_cast<float *>(w); w += sn::align_up(256 * (size_t)b, 256);
-    MdsTeamCtl *tctl = reinterpret_cast<MdsTeamCtl *>(w);
-    SN_REQUIRE(cloud_sort(b, n, xyz, bbox, hist, cell_of, perm, s) == 0, "sn_mds: cannot size the sort kernel's LDS");
+    sn::Carver carver(workspace);
+    const MdsClusteredWs w = clustered_layout(carver, b, n);
+    SN_REQUIRE(workspace && workspace_bytes >= carver.bytes(), "sn_mds: workspace too small (%zu < %zu)",
+               workspace_bytes, carver.bytes());
+    SN_REQUIRE(cloud_sort(b, n, xyz, w.bbox, w.hist, w.cell_of, w.perm, s) == 0,
+               "sn_mds: cannot size the sort kernel's LDS");
     // Dense-regime clouds go to a team of G workgroups each (mds_dense_team_kernel); the one-workgroup kernel below
     // then skips them.  G = the largest power of two <= 16 such that every cloud's team fits one XCD's share of the
     // compute units and the whole grid is resident (the members wait for each other); SN_MDS_G overrides (1: off).
@@ -1137,15 +1155,15 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
         const char *dg = SN_KNOB("SN_MDS_DIAG");
         const bool park = dg && atoi(dg) == 8;
         SN_REQUIRE(team_slots * team_g <= 1024 && pg <= 10, "sn_mds: unexpected team geometry");
-        SN_HIP(hipMemsetAsync(tctl, 0, 128 + 128 * 3 * (size_t)team_slots * team_g, s));
+        SN_HIP(hipMemsetAsync(w.tctl, 0, 128 + 128 * 3 * (size_t)team_slots * team_g, s));
         sn::PersistentLaunch chain(dev, s);  // never beside another team-waiting launch of this process (common.hpp)
 #define SN_MDST(P)                                                                                          \
   {                                                                                                         \
     SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_dense_team_kernel<P>),                   \
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));             \
     mds_dense_team_kernel<P><<<team_slots * team_g, nw * 64, (size_t)P * nw * 64 * 8, s>>>(                 \
-        b, n, m, xyz, perm, bbox, mean_mst_length, idx, tctl, sticky, team_g, team_slots, park ? 3 : 1,     \
-        park ? 1u << 14 : 1u << 24, team_ratio_eff, nw);                                                    \
+        b, n, m, xyz, w.perm, w.bbox, mean_mst_length, idx, w.tctl, sticky, team_g, team_slots,             \
+        park ? 3 : 1, park ? 1u << 14 : 1u << 24, team_ratio_eff, nw);                                      \
   }
         if (pg <= 1) SN_MDST(1)
         else if (pg <= 2) SN_MDST(2)
@@ -1166,8 +1184,8 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
        DataParallel), it is not a per-process fact */                                            \
     SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_clustered_kernel<P>),         \
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));  \
-    mds_clustered_kernel<P><<<b, 1024, lds, s>>>(n, m, xyz, perm, bbox, mean_mst_length, idx, skip_ratio, \
-                                                 recover, recovered);                                   \
+    mds_clustered_kernel<P><<<b, 1024, lds, s>>>(n, m, xyz, w.perm, w.bbox, mean_mst_length, idx, \
+                                                 skip_ratio, recover, recovered);                \
   }
     // exact slot counts near the register limit (19 at SpareNet's n = 19384): every unused
     // slot costs three VGPRs and the 1024-lane workgroup only has 128 per lane
@@ -1200,10 +1218,10 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
     SN_MDS_Z(24, 1);
   }
   else {
-    SN_REQUIRE(workspace && workspace_bytes >= sn_mds_workspace_bytes(b, n),
-               "sn_mds: workspace too small for n=%d", n);
-    mds_kernel_generic<<<b, bs, 0, s>>>(n, m, xyz, mean_mst_length,
-                                        static_cast<float *>(workspace), idx, lg);
+    sn::Carver carver(workspace);
+    float *dens = generic_layout(carver, b, n);
+    SN_REQUIRE(workspace && workspace_bytes >= carver.bytes(), "sn_mds: workspace too small for n=%d", n);
+    mds_kernel_generic<<<b, bs, 0, s>>>(n, m, xyz, mean_mst_length, dens, idx, lg);
   }
 #undef SN_MDS_Z
   if (sn::prof_enabled()) sn::prof_end("mds", s);

@@ -1281,21 +1281,50 @@ __global__ __launch_bounds__(256) void p2i_max_bwd_finish_kernel(
   }
 }
 
+// ---- the workspaces.  The global scatter: one packed {value, id} word per pixel
+unsigned long long *pixel_layout(sn::Carver &c, int batch, int channels, int h, int w) {
+  return c.take<unsigned long long>((size_t)batch * channels * h * w * 8);
+}
+// its backward: three floats per pixel
+float *pixel_bwd_layout(sn::Carver &c, int batch, int channels, int h, int w) {
+  return c.take<float>((size_t)batch * channels * h * w * 12);
+}
+// the binned gather (tile_forward)
+struct TileWs {
+  unsigned *fmax_bits;  // max |feature| (bits), for the error band; the next word != 0: the generic binning kernels
+                        // have to run
+  int *counts;          // [cells] points per cell
+  int *offs;            // [cells] cell starts
+  float4 *srec;         // [npoints] the points in cell order
+};
+TileWs tile_layout(sn::Carver &c, int npoints, int batch, int h, int w) {
+  const size_t cells = (size_t)batch * sn::ceil_div(h, kCell) * sn::ceil_div(w, kCell);
+  return {c.take<unsigned>(256), c.take256<int>(cells * 4), c.take256<int>(cells * 4),
+          c.take<float4>((size_t)npoints * 16)};
+}
+// the multi-radius backward's fixed-point accumulators
+struct AccWs {
+  unsigned *absmax;
+  long long *acc_pts;   // [npoints, 2]
+  long long *acc_feat;  // [npoints, channels]
+  unsigned *cls;        // one class byte per accumulator (non-finite terms)
+};
+AccWs acc_layout(sn::Carver &c, int npoints, int channels) {
+  return {c.take<unsigned>(256), c.take<long long>((size_t)npoints * 2 * 8),
+          c.take<long long>((size_t)npoints * channels * 8),
+          c.take<unsigned>(sn::align_up((size_t)npoints * (2 + (size_t)channels), 4))};
+}
+
 }  // namespace
 
 extern "C" size_t sn_p2i_max_workspace_bytes(int batch, int channels, int h, int w) {
   if (batch < 1 || channels < 1 || h < 1 || w < 1) return 0;
-  return (size_t)batch * channels * h * w * 8;
+  return sn::layout_bytes(pixel_layout, batch, channels, h, w);
 }
 
 namespace {
 
 constexpr float kTileMaxRadius = 16.f;  // larger kernels use the global scatter
-
-size_t tile_workspace_bytes(int npoints, int batch, int h, int w) {
-  const size_t cells = (size_t)batch * sn::ceil_div(h, kCell) * sn::ceil_div(w, kCell);
-  return 256 + 2 * sn::align_up(cells * 4, 256) + (size_t)npoints * 16;
-}
 
 // largest fp32 s with sqrtf(s) <= radius, on the host (IEEE sqrtf is correctly rounded there too)
 float max_sq_inside_host(float radius) {
@@ -1336,29 +1365,26 @@ int tile_forward(const char *fn, const float *points, const float *feat, const i
   const long cells = (long)batch * cells_x * cells_y;
   const long tiles = cells * channels;
   SN_REQUIRE(tiles / 4 + 1 < (1L << 31), "%s: too many tiles", fn);
-  char *wp = static_cast<char *>(workspace);
-  unsigned *fmax_bits = reinterpret_cast<unsigned *>(wp); wp += 256;   // max |feature| (bits), for the error band
-  unsigned *need = fmax_bits + 1;   // != 0: the generic binning kernels have to run
-  int *counts = reinterpret_cast<int *>(wp); wp += sn::align_up((size_t)cells * 4, 256);
-  int *offs = reinterpret_cast<int *>(wp); wp += sn::align_up((size_t)cells * 4, 256);
-  float4 *srec = reinterpret_cast<float4 *>(wp);
+  sn::Carver carver(workspace);
+  const TileWs t = tile_layout(carver, npoints, batch, h, w);
+  unsigned *const need = t.fmax_bits + 1;
   const bool try_grouped = npoints > 0 && npoints % batch == 0 && cells_x * cells_y <= kGroupCells;
   if (try_grouped) {
-    SN_HIP(hipMemsetAsync(fmax_bits, 0, 8, s));
-    p2i_bin_grouped_kernel<<<batch, 1024, 0, s>>>(points, feat, batch_inds, offs, srec, fmax_bits, need,
+    SN_HIP(hipMemsetAsync(t.fmax_bits, 0, 8, s));
+    p2i_bin_grouped_kernel<<<batch, 1024, 0, s>>>(points, feat, batch_inds, t.offs, t.srec, t.fmax_bits, need,
                                                   npoints / batch, channels, h, w, cells_x, cells_y);
   } else {
-    SN_HIP(hipMemsetAsync(fmax_bits, 0, 4, s));
+    SN_HIP(hipMemsetAsync(t.fmax_bits, 0, 4, s));
     SN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(need), 1, 1, s));
   }
-  SN_HIP(hipMemsetAsync(counts, 0, (size_t)cells * 4, s));
+  SN_HIP(hipMemsetAsync(t.counts, 0, (size_t)cells * 4, s));
   if (npoints > 0)
-    p2i_bin_count_kernel<<<lin_blocks(npoints), 256, 0, s>>>(points, batch_inds, counts, npoints, batch,
+    p2i_bin_count_kernel<<<lin_blocks(npoints), 256, 0, s>>>(points, batch_inds, t.counts, npoints, batch,
                                                              h, w, cells_x, cells_y, need);
-  p2i_bin_scan_kernel<<<batch, 1024, 0, s>>>(counts, offs, cells_x * cells_y, need);
+  p2i_bin_scan_kernel<<<batch, 1024, 0, s>>>(t.counts, t.offs, cells_x * cells_y, need);
   if (npoints > 0)
-    p2i_bin_scatter_kernel<<<lin_blocks(npoints), 256, 0, s>>>(points, feat, batch_inds, offs, srec, fmax_bits,
-                                                               npoints, channels, batch, h, w, cells_x,
+    p2i_bin_scatter_kernel<<<lin_blocks(npoints), 256, 0, s>>>(points, feat, batch_inds, t.offs, t.srec,
+                                                               t.fmax_bits, npoints, channels, batch, h, w, cells_x,
                                                                cells_y, need);
   const int blocks = (int)((tiles + 3) / 4);
   const long chw = (long)channels * h * w;
@@ -1366,11 +1392,11 @@ int tile_forward(const char *fn, const float *points, const float *feat, const i
 #define SN_GATHER(NR)                                                                         \
   do {                                                                                        \
     if (channels == 1)                                                                        \
-      p2i_gather_max_kernel<NR, true><<<blocks, 256, 0, s>>>(feat, background, srec, offs,      \
-          fmax_bits, channels, batch, h, w, cells_x, cells_y, ra, out, out_ids, obstride, orstride); \
+      p2i_gather_max_kernel<NR, true><<<blocks, 256, 0, s>>>(feat, background, t.srec, t.offs,   \
+          t.fmax_bits, channels, batch, h, w, cells_x, cells_y, ra, out, out_ids, obstride, orstride); \
     else                                                                                      \
-      p2i_gather_max_kernel<NR, false><<<blocks, 256, 0, s>>>(feat, background, srec, offs,     \
-          fmax_bits, channels, batch, h, w, cells_x, cells_y, ra, out, out_ids, obstride, orstride); \
+      p2i_gather_max_kernel<NR, false><<<blocks, 256, 0, s>>>(feat, background, t.srec, t.offs,  \
+          t.fmax_bits, channels, batch, h, w, cells_x, cells_y, ra, out, out_ids, obstride, orstride); \
   } while (0)
   if (sn::prof_enabled()) sn::prof_begin("p2i_max_splat", s);
   switch (nradii) {
@@ -1408,7 +1434,7 @@ extern "C" size_t sn_p2i_max_multi_workspace_bytes(int npoints, int batch, int c
                                                    int w) {
   if (npoints < 0 || batch < 1 || channels < 1 || h < 1 || w < 1) return 0;
   const size_t a = sn_p2i_max_workspace_bytes(batch, channels, h, w);
-  const size_t t = tile_workspace_bytes(npoints, batch, h, w);
+  const size_t t = sn::layout_bytes(tile_layout, npoints, batch, h, w);
   return a > t ? a : t;
 }
 
@@ -1419,13 +1445,13 @@ extern "C" int sn_p2i_max_forward(const float *points, const float *feat, const 
   SN_REQUIRE(background && out && out_ids && workspace, "sn_p2i_max_forward: null pointer");
   SN_REQUIRE(npoints == 0 || (points && feat && batch_inds), "sn_p2i_max_forward: null pointer");
   if (int rc = check_common("sn_p2i_max_forward", npoints, channels, batch, h, w, radius)) return rc;
-  SN_REQUIRE(workspace_bytes >= sn_p2i_max_workspace_bytes(batch, channels, h, w),
-             "sn_p2i_max_forward: workspace too small");
+  sn::Carver carver(workspace);
+  unsigned long long *img = pixel_layout(carver, batch, channels, h, w);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_p2i_max_forward: workspace too small");
   hipStream_t s = sn::as_stream(stream);
-  if (radius <= kTileMaxRadius && workspace_bytes >= tile_workspace_bytes(npoints, batch, h, w))
+  if (radius <= kTileMaxRadius && workspace_bytes >= sn::layout_bytes(tile_layout, npoints, batch, h, w))
     return tile_forward("sn_p2i_max_forward", points, feat, batch_inds, background, npoints,
                         channels, batch, h, w, &radius, 1, 0, out, out_ids, workspace, s);
-  unsigned long long *img = static_cast<unsigned long long *>(workspace);
   const long px = (long)batch * channels * h * w;
   p2i_max_init_kernel<<<lin_blocks(px), 256, 0, s>>>(background, img, px);
   const long groups = (long)npoints * channels;
@@ -1488,7 +1514,7 @@ extern "C" int sn_p2i_max_forward_multi(const float *points, const float *feat,
 
 extern "C" size_t sn_p2i_max_backward_workspace_bytes(int batch, int channels, int h, int w) {
   if (batch < 1 || channels < 1 || h < 1 || w < 1) return 0;
-  return (size_t)batch * channels * h * w * 12;
+  return sn::layout_bytes(pixel_bwd_layout, batch, channels, h, w);
 }
 
 extern "C" int sn_p2i_max_backward(const float *out_grad, const int *out_ids, const float *points,
@@ -1500,11 +1526,11 @@ extern "C" int sn_p2i_max_backward(const float *out_grad, const int *out_ids, co
   SN_REQUIRE(npoints == 0 || (points && feat && points_grad && feat_grad),
              "sn_p2i_max_backward: null pointer");
   if (int rc = check_common("sn_p2i_max_backward", npoints, channels, batch, h, w, radius)) return rc;
-  SN_REQUIRE(workspace_bytes >= sn_p2i_max_backward_workspace_bytes(batch, channels, h, w),
-             "sn_p2i_max_backward: workspace too small");
+  sn::Carver carver(workspace);
+  float *contrib = pixel_bwd_layout(carver, batch, channels, h, w);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_p2i_max_backward: workspace too small");
   hipStream_t s = sn::as_stream(stream);
   const long px = (long)batch * channels * h * w;
-  float *contrib = static_cast<float *>(workspace);
   p2i_max_bwd_pixels_kernel<<<lin_blocks(px), 256, 0, s>>>(out_grad, out_ids, points, feat,
                                                            background_grad, contrib, channels, h, w,
                                                            radius, px);
@@ -1527,8 +1553,7 @@ extern "C" int sn_p2i_max_backward(const float *out_grad, const int *out_ids, co
 
 extern "C" size_t sn_p2i_max_backward_multi_workspace_bytes(int npoints, int channels) {
   if (npoints < 0 || channels < 1) return 0;
-  const size_t entries = (size_t)npoints * (2 + (size_t)channels);
-  return 256 + entries * 8 + sn::align_up(entries, 4);  // + one class byte per entry (non-finite terms)
+  return sn::layout_bytes(acc_layout, npoints, channels);
 }
 
 extern "C" int sn_p2i_max_backward_multi(const float *out_grad, const int *out_ids,
@@ -1551,30 +1576,27 @@ extern "C" int sn_p2i_max_backward_multi(const float *out_grad, const int *out_i
     ra.inv_r2[k] = 1.0f / (radii[k] * radii[k]);
     rmin = radii[k] < rmin ? radii[k] : rmin;
   }
-  SN_REQUIRE(workspace_bytes >= sn_p2i_max_backward_multi_workspace_bytes(npoints, channels),
-             "sn_p2i_max_backward_multi: workspace too small");
+  sn::Carver carver(workspace);
+  const AccWs a = acc_layout(carver, npoints, channels);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_p2i_max_backward_multi: workspace too small");
   hipStream_t s = sn::as_stream(stream);
   const long px = (long)batch * channels * h * w;
-  unsigned *absmax = static_cast<unsigned *>(workspace);
-  long long *acc_pts = reinterpret_cast<long long *>(static_cast<char *>(workspace) + 256);
-  long long *acc_feat = acc_pts + (size_t)npoints * 2;
-  unsigned *cls = reinterpret_cast<unsigned *>(acc_feat + (size_t)npoints * channels);
-  SN_HIP(hipMemsetAsync(workspace, 0, sn_p2i_max_backward_multi_workspace_bytes(npoints, channels), s));
+  SN_HIP(hipMemsetAsync(workspace, 0, carver.bytes(), s));
   p2i_absmax_kernel<<<512, 1024, 0, s>>>(out_grad, px * nradii, feat,
-                                                           (long)npoints * channels, absmax);
+                                                           (long)npoints * channels, a.absmax);
   // one workgroup per region of kAccRegion x kAccRegion tiles; images b with b % 8 == x on XCD x (blockIdx % 8)
   const long per_image = (long)channels * sn::ceil_div(sn::ceil_div(h, kCell), kAccRegion) *
                          sn::ceil_div(sn::ceil_div(w, kCell), kAccRegion);
   const long blocks = per_image * 8 * ((batch + 7) / 8);
   SN_REQUIRE(blocks < (1L << 31), "sn_p2i_max_backward_multi: image too large");
-  p2i_max_bwd_accum_kernel<<<(int)blocks, 256, 0, s>>>(out_grad, out_ids, points, feat, absmax,
-                                                       background_grad, acc_pts, acc_feat, cls,
+  p2i_max_bwd_accum_kernel<<<(int)blocks, 256, 0, s>>>(out_grad, out_ids, points, feat, a.absmax,
+                                                       background_grad, a.acc_pts, a.acc_feat, a.cls,
                                                        (long)npoints * 2, channels, batch, h, w, ra, nradii, rmin,
                                                        image_major ? (long)nradii * channels * h * w : (long)channels * h * w,
                                                        image_major ? (long)channels * h * w : px);
   if (npoints > 0)
     p2i_max_bwd_finish_kernel<<<lin_blocks((long)npoints * (2 + channels)), 256, 0, s>>>(
-        acc_pts, acc_feat, absmax, cls, points_grad, feat_grad, (long)npoints * 2,
+        a.acc_pts, a.acc_feat, a.absmax, a.cls, points_grad, feat_grad, (long)npoints * 2,
         (long)npoints * channels, rmin);
   return sn::launch_status("sn_p2i_max_backward_multi");
 }

@@ -169,11 +169,16 @@ int check64(const char *fn, int npoints, int channels, int batch, int h, int w, 
   return 0;
 }
 
+// the workspace: one packed key per pixel
+unsigned long long *key_layout(sn::Carver &c, int batch, int channels, int h, int w) {
+  return c.take<unsigned long long>((size_t)batch * channels * h * w * 8);
+}
+
 }  // namespace
 
 extern "C" size_t sn_p2i_f64_workspace_bytes(int batch, int channels, int h, int w) {
   if (batch < 1 || channels < 1 || h < 1 || w < 1) return 0;
-  return (size_t)batch * channels * h * w * 8;
+  return sn::layout_bytes(key_layout, batch, channels, h, w);
 }
 
 extern "C" int sn_p2i_max_forward_f64(const double *points, const double *feat, const int *batch_inds,
@@ -183,11 +188,11 @@ extern "C" int sn_p2i_max_forward_f64(const double *points, const double *feat, 
   SN_REQUIRE(background && out && out_ids && workspace, "sn_p2i_max_forward_f64: null pointer");
   SN_REQUIRE(npoints == 0 || (points && feat && batch_inds), "sn_p2i_max_forward_f64: null pointer");
   if (int rc = check64("sn_p2i_max_forward_f64", npoints, channels, batch, h, w, radius)) return rc;
-  SN_REQUIRE(workspace_bytes >= sn_p2i_f64_workspace_bytes(batch, channels, h, w),
-             "sn_p2i_max_forward_f64: workspace too small");
+  sn::Carver carver(workspace);
+  unsigned long long *key = key_layout(carver, batch, channels, h, w);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_p2i_max_forward_f64: workspace too small");
   hipStream_t s = sn::as_stream(stream);
   const long total = (long)batch * channels * h * w;
-  unsigned long long *key = static_cast<unsigned long long *>(workspace);
   f64_init_kernel<<<blocks_of(total), 256, 0, s>>>(background, total, key, out_ids);
   const long groups = (long)npoints * channels;
   if (groups > 0) {

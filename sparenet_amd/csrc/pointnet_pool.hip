@@ -173,13 +173,21 @@ __global__ __launch_bounds__(256) void pn_reduce_kernel(const float *__restrict_
 }
 
 inline int pn_tiles(int n) { return (n + kTile - 1) / kTile; }
-constexpr size_t kW3tBytes = (size_t)kC2 * kC3 * 4, kW2tBytes = (size_t)kC1 * kC2 * 4;
+
+struct PoolWs {  // the workspace
+  float *w3t, *w2t;  // the transposed weights of layers 3 and 2
+  float *partial;    // [b, tiles, kC3] per-tile maxima
+};
+PoolWs pool_layout(sn::Carver &c, int b, int n) {
+  return {c.take<float>((size_t)kC2 * kC3 * 4), c.take<float>((size_t)kC1 * kC2 * 4),
+          c.take256<float>((size_t)b * pn_tiles(n) * kC3 * 4)};
+}
 
 }  // namespace
 
 extern "C" size_t sn_pointnet_pool_workspace_bytes(int b, int n) {
   if (b < 1 || n < 1 || n > (1 << 20)) return 0;
-  return kW3tBytes + kW2tBytes + sn::align_up((size_t)b * pn_tiles(n) * kC3 * 4, 256);
+  return sn::layout_bytes(pool_layout, b, n);
 }
 
 extern "C" int sn_pointnet_pool_forward(const float *xyz, const float *trans, const float *w1, const float *b1,
@@ -192,19 +200,17 @@ extern "C" int sn_pointnet_pool_forward(const float *xyz, const float *trans, co
   const int ntiles = pn_tiles(n);
   SN_REQUIRE((long long)b * ntiles <= 0x7fffffffLL && b <= (1 << 26),
              "sn_pointnet_pool_forward: batch too large (b = %d, %d tiles per cloud)", b, ntiles);
-  SN_REQUIRE(workspace_bytes >= sn_pointnet_pool_workspace_bytes(b, n),
-             "sn_pointnet_pool_forward: workspace too small (%zu bytes, need %zu)", workspace_bytes,
-             sn_pointnet_pool_workspace_bytes(b, n));
+  sn::Carver carver(workspace);
+  const PoolWs w = pool_layout(carver, b, n);
+  SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_pointnet_pool_forward: workspace too small (%zu bytes, need %zu)",
+             workspace_bytes, carver.bytes());
   hipStream_t s = sn::as_stream(stream);
-  float *w3t = static_cast<float *>(workspace);
-  float *w2t = w3t + kC2 * kC3;
-  float *partial = w2t + kC1 * kC2;
-  pn_transpose_kernel<<<kC2 * kC3 / 256, 256, 0, s>>>(w2, w3, w2t, w3t);
+  pn_transpose_kernel<<<kC2 * kC3 / 256, 256, 0, s>>>(w2, w3, w.w2t, w.w3t);
   SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pn_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)kLdsBytes));  // per call: the attribute belongs to the current device
   SN_TIMED("pointnet_pool", s,
-           (pn_pool_kernel<<<(unsigned)(b * ntiles), 256, kLdsBytes, s>>>(xyz, trans, w1, b1, w2t, b2, w3t, n, ntiles,
-                                                                         partial)));
-  pn_reduce_kernel<<<(unsigned)b * (kC3 / 64), 256, 0, s>>>(partial, b3, ntiles, relu_last, out);
+           (pn_pool_kernel<<<(unsigned)(b * ntiles), 256, kLdsBytes, s>>>(xyz, trans, w1, b1, w.w2t, b2, w.w3t, n,
+                                                                         ntiles, w.partial)));
+  pn_reduce_kernel<<<(unsigned)b * (kC3 / 64), 256, 0, s>>>(w.partial, b3, ntiles, relu_last, out);
   return sn::launch_status("sn_pointnet_pool_forward");
 }
