@@ -13,13 +13,11 @@ Same public names, state-dict keys and shapes as the reference's Frechet/pointne
 FPD is an evaluation metric: there is NO autograd through the fused op, `forward` runs under `torch.no_grad()`,
 and training mode raises (batch statistics would need the per-point activations).  PointNetDenseCls is not provided.
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .._lib import check, fptr, lib, stream_of
+from .. import _lib
 
 
 def fold_batch_norm(layer, bn, dtype):
@@ -51,19 +49,12 @@ def pool_mlp_fused(x, trans, folded, relu_last):
         raise TypeError(f"the fused PointNet kernel is fp32 only, got {x.dtype}")
     (w1, b1), (w2, b2), (w3, b3) = folded
     xyz = x.transpose(2, 1).contiguous()
-    fptr(xyz, "x")   # raises for a CPU tensor: this op has no other path
+    _lib.require_device(xyz, "x")   # raises for a CPU tensor: this op has no other path
     b, n = xyz.shape[0], xyz.shape[1]
     out = torch.empty(b, 1024, dtype=torch.float32, device=x.device)
-    L = lib()
-    nbytes = int(L.sn_pointnet_pool_workspace_bytes(b, n))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
-    trans = None if trans is None else trans.contiguous()   # held until the launch is enqueued
-    tptr = ctypes.c_void_p(0) if trans is None else fptr(trans, "trans")
-    with torch.cuda.device(x.device):
-        check(L.sn_pointnet_pool_forward(fptr(xyz, "xyz"), tptr, fptr(w1, "w1"), fptr(b1, "b1"), fptr(w2, "w2"),
-                                         fptr(b2, "b2"), fptr(w3, "w3"), fptr(b3, "b3"), int(bool(relu_last)), b, n,
-                                         fptr(out, "out"), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes),
-                                         stream_of(x)), "sn_pointnet_pool_forward")
+    ws = _lib.workspace("sn_pointnet_pool_workspace_bytes", xyz, b, n)
+    trans = None if trans is None else trans.contiguous()   # None: a null pointer, the identity
+    _lib.call("sn_pointnet_pool_forward", xyz, trans, w1, b1, w2, b2, w3, b3, bool(relu_last), b, n, out, ws)
     return out
 
 

@@ -6,7 +6,7 @@ meaning as /root/reference/cuda/* and utils/p2i_utils.py); every op calls the
 hand-written HIP kernels in libsparenet_hip.so through the C ABI declared in
 include/sparenet_hip.h.  There is no CPU or eager-PyTorch fallback.
 """
-from ._lib import LIB_PATH, SparenetHipError, device_check, lib  # noqa: F401
+from ._lib import LIB_PATH, SparenetHipError, call, device_check, lib  # noqa: F401
 
 __version__ = "0.1.0"
 
@@ -26,14 +26,12 @@ def set_wait_policy(name):
     "recover"."""
     if name not in WAIT_POLICIES:
         raise ValueError(f"unknown wait policy {name!r}: expected one of {', '.join(WAIT_POLICIES)}")
-    from ._lib import check
-
-    check(lib().sn_set_wait_policy(WAIT_POLICIES.index(name)), "sn_set_wait_policy")
+    call("sn_set_wait_policy", WAIT_POLICIES.index(name))
 
 
 def wait_policy():
     """The current wait policy's name (see set_wait_policy)."""
-    return WAIT_POLICIES[lib().sn_wait_policy()]
+    return WAIT_POLICIES[call("sn_wait_policy")]
 
 
 def wait_report():
@@ -42,10 +40,8 @@ def wait_report():
     covers work that has finished (call it after a `.item()` / synchronize)."""
     import ctypes
 
-    from ._lib import check
-
     out = (ctypes.c_longlong * 3)()
-    check(lib().sn_wait_report(out, 3), "sn_wait_report")
+    call("sn_wait_report", out, 3)
     return {"emd_recovered": int(out[0]), "mds_recovered": int(out[1]), "latched": bool(out[2])}
 
 

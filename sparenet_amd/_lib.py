@@ -1,17 +1,24 @@
 """ctypes binding of libsparenet_hip.so (the C ABI declared in include/sparenet_hip.h).
 
-There is deliberately NO fallback: if the HIP library is missing, or a tensor is
-not a contiguous CUDA(ROCm) tensor of the right dtype, these helpers raise.
-PyTorch is used only for device memory and streams.
+The header is the single description of a call: `prototypes()` parses it, `lib()` derives the ctypes signatures and
+one prepared parameter list per function from that parse, and `call()` / `workspace()` are the one path on which
+Python values become C arguments -- checked against the declared pointee type, under the declared parameter name.
+
+There is deliberately NO fallback: if the HIP library or its header is missing, or a tensor is not a contiguous
+CUDA(ROCm) tensor of the declared dtype, these helpers raise.  PyTorch is used only for device memory and streams.
 """
+import collections
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsparenet_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sparenet_hip.h")
 _lib = None
+_calls = {}     # name -> (ctypes function, prepared parameters, has a trailing stream, int result is a status code)
 
 SN_EINVAL = -22
 
@@ -25,59 +32,92 @@ class SparenetHipError(RuntimeError):
 # arguments -- memory corruption instead of an error -- so lib() refuses any other version.
 EXPECTED_ABI = 4
 
-_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
-           "long long": ctypes.c_longlong, "long": ctypes.c_long, "unsigned": ctypes.c_uint, "void": None}
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+# pointee type -> (dtype a tensor must have, element type a host ctypes array must have); void takes any tensor
+_POINTEES = {"float": (torch.float32, ctypes.c_float), "int": (torch.int32, ctypes.c_int),
+             "double": (torch.float64, ctypes.c_double), "long long": (torch.int64, ctypes.c_longlong),
+             "unsigned": (torch.int32, ctypes.c_uint), "void": (None, None), "char": (None, ctypes.c_char)}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "void": None,
+            "const char *": ctypes.c_char_p}
+
+Param = collections.namedtuple("Param", "name ctype pointer const")     # `const float *xyz1`: xyz1, float, True, True
+Workspace = collections.namedtuple("Workspace", "tensor nbytes")        # a uint8 tensor and its size export's answer
+
+_POINTER, _WORKSPACE, _INTEGER, _REAL, _TEXT = range(5)
 
 
-def _prototypes():
-    """{name: (restype, [argtypes])} parsed from include/sparenet_hip.h, or {} when the header is not shipped
-    next to the package (the version check above still applies)."""
-    import re
-
-    hdr = os.path.join(os.path.dirname(_HERE), "include", "sparenet_hip.h")
-    if not os.path.isfile(hdr):
-        return {}
-    txt = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
+def prototypes(path=None):
+    """{name: (return type, [Param, ...])} of every function include/sparenet_hip.h declares."""
+    txt = re.sub(r"/\*.*?\*/", "", open(path or HEADER_PATH).read(), flags=re.S)
     out = {}
     for m in re.finditer(r"^(int|size_t|void|long long|const char \*)\s*(sn_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt,
                          re.M | re.S):
-        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
-        types = []
-        if args not in ("", "void"):
-            for a in args.split(","):
-                a = " ".join(a.split())
-                if "*" in a:
-                    types.append(ctypes.c_char_p if a.startswith("const char") else ctypes.c_void_p)
-                else:
-                    base = a.rsplit(" ", 1)[0].replace("const ", "").strip()
-                    types.append(_CTYPES[base])
-        out[name] = (ctypes.c_char_p if "char" in ret else _CTYPES[ret], types)
+        args = m.group(3).strip()
+        params = []
+        for a in ([] if args in ("", "void") else args.split(",")):
+            p = re.fullmatch(r"(const )?([a-z_ ]+?) ?(\*)? ?(\w+)", " ".join(a.split()))
+            params.append(Param(p.group(4), p.group(2), bool(p.group(3)), bool(p.group(1))))
+        out[m.group(2)] = (m.group(1), params)
     return out
 
 
+def _prepare(params):
+    """The parameters `call` takes for a declared parameter list, as (kind, name, dtype, element type) -- without the
+    trailing `void *stream`, and with `void *workspace, size_t workspace_bytes` as one -- and whether there is a stream."""
+    has_stream = bool(params) and params[-1] == Param("stream", "void", True, False)
+    steps = []
+    for i, p in enumerate(params[:len(params) - has_stream]):
+        if p.pointer and p.ctype == "char":
+            steps.append((_TEXT, p.name, None, None))
+        elif p.pointer:
+            sized = p.name == "workspace" and params[i + 1:i + 2] == [Param("workspace_bytes", "size_t", False, False)]
+            steps.append((_WORKSPACE if sized else _POINTER, p.name) + _POINTEES[p.ctype])
+        elif steps and steps[-1][0] == _WORKSPACE and p.name == "workspace_bytes":
+            continue
+        else:
+            steps.append((_REAL if p.ctype in ("float", "double") else _INTEGER, p.name, None, _SCALARS[p.ctype]))
+    return steps, has_stream
+
+
 def lib():
-    """Load (once) and return the HIP library; raises if it is not built or was built for another ABI."""
+    """Load (once) and return the HIP library; raises if it is not built, was built for another ABI, or the header
+    that describes its calls is not next to the package."""
     global _lib
     if _lib is None:
         if not os.path.isfile(LIB_PATH):
             raise SparenetHipError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` or `make -C sparenet_amd/csrc`. sparenet_amd has no CPU fallback.")
+        if not os.path.isfile(HEADER_PATH):
+            raise SparenetHipError(
+                f"{HEADER_PATH} not found: the header is the description of every call into {LIB_PATH} (argument "
+                "types, names and counts); the library is not loaded without it.")
         L = ctypes.CDLL(LIB_PATH)
         got = L.sn_abi_version()
         if got != EXPECTED_ABI:
             raise SparenetHipError(
                 f"{LIB_PATH} implements C ABI version {got}, this Python side needs {EXPECTED_ABI}: rebuild the "
                 "library (`make -C sparenet_amd/csrc`)")
-        L.sn_last_error.restype = ctypes.c_char_p
-        L.sn_build_id.restype = ctypes.c_char_p
-        for name, (ret, args) in _prototypes().items():
+        _calls.clear()
+        for name, (ret, params) in prototypes().items():
             fn = getattr(L, name, None)
-            if fn is not None:      # a missing export is test_abi's finding, not a load-time failure
-                fn.restype = ret
-                fn.argtypes = args
+            if fn is None:          # a missing export is test_abi's finding, not a load-time failure
+                continue
+            fn.restype = _RETURNS[ret]
+            fn.argtypes = [(ctypes.c_char_p if p.ctype == "char" else ctypes.c_void_p) if p.pointer
+                           else _SCALARS[p.ctype] for p in params]
+            # an int function WITH parameters returns a status code; one without (sn_wait_policy, sn_emd_mode,
+            # sn_device_status ...) is a query whose number goes back to the caller
+            _calls[name] = (fn,) + _prepare(params) + (ret == "int" and bool(params),)
         _lib = L
     return _lib
+
+
+def signature(name):
+    """Names of the arguments `call(name, ...)` takes, in order."""
+    lib()
+    return [step[1] for step in _calls[name][1]]
 
 
 def check(code, what):
@@ -92,36 +132,120 @@ def device_check(what="sparenet_amd"):
     host memory (sn_device_status): no synchronisation -- meaningful for work that has FINISHED, so the wrappers call
     it on entry (an earlier step's failure surfaces at the next op) and `loss_item` calls it where the host has just
     waited for the loss."""
-    check(lib().sn_device_status(), what)
+    check(call("sn_device_status"), what)
 
 
-def ptr(t, dtype, name):
-    """Device pointer of a contiguous CUDA tensor (validated)."""
+def _address(t, dtype, name, host=False):
+    """Address of a contiguous tensor on the expected side (device, or host for the Chamfer host entry points) and of
+    the expected dtype (None: any)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a torch.Tensor")
-    if not t.is_cuda:
+    if t.is_cuda == host:
+        if host:
+            raise SparenetHipError(f"{name}: expected a CPU tensor, got device {t.device}")
         raise SparenetHipError(
             f"{name}: expected a CUDA (ROCm) tensor, got device {t.device}. sparenet_amd runs on "
             "MI355X only; there is no CPU path for this op (the reference has none either; only ChamferDistance "
             "accepts CPU tensors, as in the reference).")
-    if t.dtype != dtype:
+    if dtype is not None and t.dtype != dtype:
         raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
     if not t.is_contiguous():
         raise ValueError(f"{name}: tensor must be contiguous")
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
+
+
+def require_device(t, name):
+    """Refuse a CPU tensor (or a non-tensor) with the message of a device entry point, before a wrapper uploads or
+    allocates anything for it."""
+    _address(t, None, name)
+
+
+def call(name, *args, host=False):
+    """Call the declared function `name`.  `args` are its parameters in the header's order, without the trailing
+    `void *stream` (the current stream of the tensors' device is passed) and with ONE value -- a `workspace()` or
+    None -- for `void *workspace, size_t workspace_bytes`.  Per declared type: a typed pointer takes a contiguous
+    device tensor of that dtype (`host=True`: a CPU tensor, and no stream), None (a null pointer; the library says
+    where that is allowed) or a host ctypes array of that element type; integers must be integral.  All device tensors
+    must share one device, and the call runs under it.  A status code goes through check(); size_t / long long
+    functions and parameterless queries return their number."""
+    spec = _calls.get(name)
+    if spec is None:
+        lib()
+        spec = _calls.get(name)
+        if spec is None:
+            raise SparenetHipError(f"{name} is not declared in {HEADER_PATH} or not exported by {LIB_PATH}")
+    fn, steps, has_stream, is_status = spec
+    if len(args) != len(steps):
+        raise TypeError(f"{name} takes {len(steps)} arguments ({', '.join(s[1] for s in steps)}), got {len(args)}")
+    c = []
+    first = dev = None      # the first device tensor (it decides device and stream) and its device index
+    for (kind, pname, dtype, ctype), v in zip(steps, args):
+        if kind == _INTEGER:
+            i = int(v)
+            if i != v:
+                raise TypeError(f"{name}: {pname} must be an integer, got {v!r}")
+            c.append(i)
+        elif kind == _REAL:
+            c.append(float(v))
+        elif kind == _TEXT:
+            c.append(v)
+        else:
+            if kind == _WORKSPACE and v is not None:
+                if not isinstance(v, Workspace):
+                    raise TypeError(f"{name}: {pname} takes a workspace() or None")
+                v, nbytes = v
+            # the accepted tensor first and inline (this loop is the host cost of every op); _address has the refusals
+            if (isinstance(v, torch.Tensor) and v.is_cuda != host and (dtype is None or v.dtype == dtype)
+                    and v.is_contiguous()):
+                c.append(v.data_ptr())
+                if not host:
+                    if first is None:
+                        first, dev = v, v.get_device()
+                    elif v.get_device() != dev:
+                        raise ValueError(f"{name}: {pname} is on {v.device}, earlier tensor arguments on "
+                                         f"{first.device}")
+            elif v is None:
+                c.append(None)
+            elif isinstance(v, ctypes.Array):
+                if v._type_ is not ctype:
+                    raise TypeError(f"{name}: {pname} expected a host array of {ctype.__name__}, "
+                                    f"got {v._type_.__name__}")
+                c.append(v)
+            else:
+                c.append(_address(v, dtype, pname, host))      # raises: which check failed, in its documented order
+            if kind == _WORKSPACE:
+                c.append(0 if v is None else nbytes)
+    if first is None:
+        if has_stream:
+            c.append(None)
+        result = fn(*c)
+    else:
+        with torch.cuda.device_of(first):
+            if has_stream:
+                c.append(stream_of(first))
+            result = fn(*c)
+    if is_status:
+        return check(result, name) if result else None
+    return result
+
+
+def workspace(size_export, like, *shape):
+    """The scratch buffer of an op: `size_export(*shape)` is asked under `like`'s device (some layouts depend on its
+    compute-unit count), and a uint8 tensor of that size -- at least one byte, so that it has an address -- is
+    allocated there.  `call` passes the exported size, not the tensor's."""
+    with torch.cuda.device_of(like):
+        nbytes = call(size_export, *shape)
+        return Workspace(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=like.device), nbytes)
+
+
+def ptr(t, dtype, name, host=False):
+    """Device (host=True: host) pointer of a contiguous tensor (validated)."""
+    return ctypes.c_void_p(_address(t, dtype, name, host))
 
 
 def hptr(t, dtype, name):
     """HOST pointer of a contiguous CPU tensor (validated) -- only the Chamfer host entry points take these."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor")
-    if t.is_cuda:
-        raise SparenetHipError(f"{name}: expected a CPU tensor, got device {t.device}")
-    if t.dtype != dtype:
-        raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: tensor must be contiguous")
-    return ctypes.c_void_p(t.data_ptr())
+    return ptr(t, dtype, name, host=True)
 
 
 def fptr(t, name):

@@ -9,8 +9,6 @@ sn_gather_backward (include/sparenet_hip.h).
     gather_operation(features [B,C,N], idx [B,npoint]) -> [B,C,npoint], differentiable in
         features.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -26,14 +24,8 @@ class MinimumDensitySampling(Function):
         mean_mst_length = mean_mst_length.contiguous().float()
         b, n, _ = xyz.shape
         idx = torch.empty(b, npoint, device=xyz.device, dtype=torch.int32)
-        with torch.cuda.device_of(xyz):
-            nbytes = _lib.lib().sn_mds_workspace_bytes(b, n)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=xyz.device)
-            code = _lib.lib().sn_mds(
-                _lib.fptr(xyz, "xyz"), b, n, int(npoint),
-                _lib.fptr(mean_mst_length, "mean_mst_length"), _lib.iptr(idx, "idx"),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes), _lib.stream_of(xyz))
-        _lib.check(code, "sn_mds")
+        ws = _lib.workspace("sn_mds_workspace_bytes", xyz, b, n)
+        _lib.call("sn_mds", xyz, b, n, npoint, mean_mst_length, idx, ws)
         ctx.mark_non_differentiable(idx)
         return idx
 
@@ -54,11 +46,7 @@ class GatherOperation(Function):
         m = idx.size(1)
         ctx.for_backwards = (idx, c, n)
         out = torch.empty(b, c, m, device=features.device)
-        with torch.cuda.device_of(features):
-            code = _lib.lib().sn_gather_forward(
-                _lib.fptr(features, "features"), _lib.iptr(idx, "idx"), b, c, n, m,
-                _lib.fptr(out, "out"), _lib.stream_of(features))
-        _lib.check(code, "sn_gather_forward")
+        _lib.call("sn_gather_forward", features, idx, b, c, n, m, out)
         return out
 
     @staticmethod
@@ -67,11 +55,7 @@ class GatherOperation(Function):
         grad_out = grad_out.contiguous().float()
         b, _, m = grad_out.shape
         grad_features = torch.empty(b, c, n, device=grad_out.device)
-        with torch.cuda.device_of(grad_out):
-            code = _lib.lib().sn_gather_backward(
-                _lib.fptr(grad_out, "grad_out"), _lib.iptr(idx, "idx"), b, c, n, m,
-                _lib.fptr(grad_features, "grad_features"), _lib.stream_of(grad_out))
-        _lib.check(code, "sn_gather_backward")
+        _lib.call("sn_gather_backward", grad_out, idx, b, c, n, m, grad_features)
         return grad_features, None
 
 

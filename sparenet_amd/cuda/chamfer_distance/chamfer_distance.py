@@ -8,8 +8,6 @@ cd.backward): the library's own host implementation (sn_chamfer_*_host, csrc/cha
 bit-equal to the reference's CPU code.  It is the ONLY op with a host path, because it is the only
 one the reference gives one; CUDA tensors never take it.
 """
-import ctypes
-
 import torch
 
 from sparenet_amd import _lib
@@ -28,66 +26,37 @@ class _CdBinding:
         m = xyz2.shape[1]
         if n * m >= _CdBinding.SORTED_MIN_PAIRS and b * max(n, m) < (1 << 26):
             return _CdBinding.forward_sorted_cuda(xyz1, xyz2, dist1, dist2, idx1, idx2)
-        with torch.cuda.device_of(xyz1):
-            code = _lib.lib().sn_chamfer_forward(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), b, n, m,
-                _lib.fptr(dist1, "dist1"), _lib.iptr(idx1, "idx1"),
-                _lib.fptr(dist2, "dist2"), _lib.iptr(idx2, "idx2"), _lib.stream_of(xyz1))
-        _lib.check(code, "sn_chamfer_forward")
+        _lib.call("sn_chamfer_forward", xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2)
 
     @staticmethod
     def forward_sorted_cuda(xyz1, xyz2, dist1, dist2, idx1, idx2):
         """sn_chamfer_forward_sorted: identical outputs through a spatially pruned search."""
-        import ctypes
         b, n, _ = xyz1.shape
         m = xyz2.shape[1]
-        with torch.cuda.device_of(xyz1):
-            nbytes = _lib.lib().sn_chamfer_workspace_bytes(b, n, m)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz1.device)
-            code = _lib.lib().sn_chamfer_forward_sorted(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), b, n, m,
-                _lib.fptr(dist1, "dist1"), _lib.iptr(idx1, "idx1"),
-                _lib.fptr(dist2, "dist2"), _lib.iptr(idx2, "idx2"),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes), _lib.stream_of(xyz1))
-        _lib.check(code, "sn_chamfer_forward_sorted")
+        ws = _lib.workspace("sn_chamfer_workspace_bytes", xyz1, b, n, m)
+        _lib.call("sn_chamfer_forward_sorted", xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, ws)
 
     @staticmethod
     def backward_cuda(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
         b, n, _ = xyz1.shape
         m = xyz2.shape[1]
-        with torch.cuda.device_of(xyz1):
-            nbytes = _lib.lib().sn_chamfer_backward_workspace_bytes(b, n, m)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz1.device)   # inverse neighbour lists
-            code = _lib.lib().sn_chamfer_backward(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"),
-                _lib.fptr(graddist1, "graddist1"), _lib.fptr(graddist2, "graddist2"),
-                _lib.iptr(idx1, "idx1"), _lib.iptr(idx2, "idx2"), b, n, m,
-                _lib.fptr(gradxyz1, "gradxyz1"), _lib.fptr(gradxyz2, "gradxyz2"),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes), _lib.stream_of(xyz1))
-        _lib.check(code, "sn_chamfer_backward")
+        ws = _lib.workspace("sn_chamfer_backward_workspace_bytes", xyz1, b, n, m)   # inverse neighbour lists
+        _lib.call("sn_chamfer_backward", xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m, gradxyz1, gradxyz2, ws)
 
     @staticmethod
     def forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
         """cd.forward (chamfer_distance.cpp:91-112): host tensors, caller-allocated outputs."""
         b, n, _ = xyz1.shape
         m = xyz2.shape[1]
-        code = _lib.lib().sn_chamfer_forward_host(
-            _lib.hptr(xyz1, torch.float32, "xyz1"), _lib.hptr(xyz2, torch.float32, "xyz2"), b, n, m,
-            _lib.hptr(dist1, torch.float32, "dist1"), _lib.hptr(idx1, torch.int32, "idx1"),
-            _lib.hptr(dist2, torch.float32, "dist2"), _lib.hptr(idx2, torch.int32, "idx2"), 0)
-        _lib.check(code, "sn_chamfer_forward_host")
+        _lib.call("sn_chamfer_forward_host", xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, 0, host=True)
 
     @staticmethod
     def backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
         """cd.backward (chamfer_distance.cpp:114-180): host tensors; the gradients are fully overwritten."""
         b, n, _ = xyz1.shape
         m = xyz2.shape[1]
-        code = _lib.lib().sn_chamfer_backward_host(
-            _lib.hptr(xyz1, torch.float32, "xyz1"), _lib.hptr(xyz2, torch.float32, "xyz2"),
-            _lib.hptr(graddist1, torch.float32, "graddist1"), _lib.hptr(graddist2, torch.float32, "graddist2"),
-            _lib.hptr(idx1, torch.int32, "idx1"), _lib.hptr(idx2, torch.int32, "idx2"), b, n, m,
-            _lib.hptr(gradxyz1, torch.float32, "gradxyz1"), _lib.hptr(gradxyz2, torch.float32, "gradxyz2"), 0)
-        _lib.check(code, "sn_chamfer_backward_host")
+        _lib.call("sn_chamfer_backward_host", xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m,
+                  gradxyz1, gradxyz2, 0, host=True)
 
 
 cd = _CdBinding()

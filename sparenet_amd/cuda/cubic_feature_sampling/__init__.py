@@ -24,12 +24,7 @@ class CubicFeatureSamplingFunction(torch.autograd.Function):
         dev = ptcloud.device
         out = torch.empty(b, n, nv, c, device=dev)
         idx = torch.empty(b, n, nv, dtype=torch.int32, device=dev)
-        with torch.cuda.device_of(ptcloud):
-            code = _lib.lib().sn_cubic_forward(
-                _lib.fptr(ptcloud, "ptcloud"), _lib.fptr(cubic_features, "cubic_features"),
-                b, n, c, scale, ns, _lib.fptr(out, "point_features"),
-                _lib.iptr(idx, "grid_pt_indexes"), _lib.stream_of(ptcloud))
-        _lib.check(code, "sn_cubic_forward")
+        _lib.call("sn_cubic_forward", ptcloud, cubic_features, b, n, c, scale, ns, out, idx)
         ctx.dims = (b, n, c, scale, ns)
         ctx.save_for_backward(idx)
         return out
@@ -41,12 +36,7 @@ class CubicFeatureSamplingFunction(torch.autograd.Function):
         grad_point_features = grad_point_features.contiguous().float()
         dev = grad_point_features.device
         grad_cubic = torch.empty(b, c, scale, scale, scale, device=dev)
-        with torch.cuda.device_of(grad_point_features):
-            code = _lib.lib().sn_cubic_backward(
-                _lib.fptr(grad_point_features, "grad_point_features"),
-                _lib.iptr(idx, "grid_pt_indexes"), b, n, c, scale, ns,
-                _lib.fptr(grad_cubic, "grad_cubic_features"), _lib.stream_of(grad_point_features))
-        _lib.check(code, "sn_cubic_backward")
+        _lib.call("sn_cubic_backward", grad_point_features, idx, b, n, c, scale, ns, grad_cubic)
         grad_ptcloud = torch.zeros(b, n, 3, device=dev)
         return grad_ptcloud, grad_cubic, None
 

@@ -13,18 +13,11 @@ For n == m, n % 1024 == 0 the results equal emdModule's bit for bit (those sizes
 SN_EMD_GENERAL=1 forces the general kernels, which compute the same).  Backed by sn_emd_forward_general /
 sn_emd_backward_general (include/sparenet_hip.h).
 """
-import ctypes
-
 import torch
 from torch import nn
 from torch.autograd import Function
 
 from sparenet_amd import _lib
-
-
-def _workspace(b, n, m, dev):
-    nbytes = _lib.lib().sn_emd_general_workspace_bytes(b, n, m)
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
 
 
 def emd_general_forward_raw(xyz1, xyz2, eps, iters, stats=None):
@@ -35,14 +28,8 @@ def emd_general_forward_raw(xyz1, xyz2, eps, iters, stats=None):
     dev = xyz1.device
     dist = torch.empty(b, n, device=dev)
     assignment = torch.empty(b, n, device=dev, dtype=torch.int32)
-    with torch.cuda.device_of(xyz1):
-        ws, nbytes = _workspace(b, n, m, dev)
-        sp = ctypes.c_void_p(stats.data_ptr()) if stats is not None else ctypes.c_void_p(0)
-        code = _lib.lib().sn_emd_forward_general(
-            _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), b, n, m, _lib.cfloat(eps), int(iters),
-            _lib.fptr(dist, "dist"), _lib.iptr(assignment, "assignment"), ctypes.c_void_p(ws.data_ptr()),
-            ctypes.c_size_t(nbytes), sp, _lib.stream_of(xyz1))
-    _lib.check(code, "sn_emd_forward_general")
+    ws = _lib.workspace("sn_emd_general_workspace_bytes", xyz1, b, n, m)
+    _lib.call("sn_emd_forward_general", xyz1, xyz2, b, n, m, eps, iters, dist, assignment, ws, stats)
     return dist, assignment
 
 
@@ -50,22 +37,10 @@ def emd_general_backward_raw(xyz1, xyz2, graddist, assignment, need_xyz2=True):
     """(gradxyz1, gradxyz2 or None) for contiguous fp32 CUDA tensors."""
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
-    dev = xyz1.device
     gradxyz1 = torch.empty_like(xyz1)
-    gradxyz2 = torch.empty_like(xyz2) if need_xyz2 else None
-    with torch.cuda.device_of(xyz1):
-        if need_xyz2:
-            nbytes = _lib.lib().sn_emd_general_backward_workspace_bytes(b, n, m)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            wp = ctypes.c_void_p(ws.data_ptr())
-        else:
-            wp, nbytes = ctypes.c_void_p(0), 0
-        g2 = _lib.fptr(gradxyz2, "gradxyz2") if need_xyz2 else ctypes.c_void_p(0)
-        code = _lib.lib().sn_emd_backward_general(
-            _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), _lib.fptr(graddist, "graddist"),
-            _lib.iptr(assignment, "assignment"), b, n, m, _lib.fptr(gradxyz1, "gradxyz1"), g2, wp,
-            ctypes.c_size_t(nbytes), _lib.stream_of(xyz1))
-    _lib.check(code, "sn_emd_backward_general")
+    gradxyz2 = torch.empty_like(xyz2) if need_xyz2 else None      # None: a null pointer, and no workspace is needed
+    ws = _lib.workspace("sn_emd_general_backward_workspace_bytes", xyz1, b, n, m) if need_xyz2 else None
+    _lib.call("sn_emd_backward_general", xyz1, xyz2, graddist, assignment, b, n, m, gradxyz1, gradxyz2, ws)
     return gradxyz1, gradxyz2
 
 

@@ -11,8 +11,6 @@ Output: dist [#batch, #points] (sqrt(dist) -> L2 distance), assignment
 Backed by sn_emd_forward / sn_emd_backward (include/sparenet_hip.h); the twelve
 scratch tensors the reference allocates per call (:43-54) are one workspace here.
 """
-import ctypes
-
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -27,17 +25,10 @@ def emd_forward_raw(xyz1, xyz2, eps, iters, stats=None, return_workspace=False):
     dev = xyz1.device
     dist = torch.empty(batchsize, n, device=dev)
     assignment = torch.empty(batchsize, n, device=dev, dtype=torch.int32)
-    with torch.cuda.device_of(xyz1):
-        nbytes = _lib.lib().sn_emd_workspace_bytes(batchsize, n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        sp = ctypes.c_void_p(stats.data_ptr()) if stats is not None else ctypes.c_void_p(0)
-        code = _lib.lib().sn_emd_forward(
-            _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), batchsize, n, _lib.cfloat(eps),
-            int(iters), _lib.fptr(dist, "dist"), _lib.iptr(assignment, "assignment"),
-            ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes), sp, _lib.stream_of(xyz1))
-    _lib.check(code, "sn_emd_forward")
+    ws = _lib.workspace("sn_emd_workspace_bytes", xyz1, batchsize, n)
+    _lib.call("sn_emd_forward", xyz1, xyz2, batchsize, n, eps, iters, dist, assignment, ws, stats)
     if return_workspace:
-        return dist, assignment, ws
+        return dist, assignment, ws.tensor
     return dist, assignment
 
 
@@ -68,12 +59,7 @@ class emdFunction(Function):
         gradxyz1 = torch.empty_like(xyz1)
         gradxyz2 = torch.zeros_like(xyz2)
         b, n, _ = xyz1.shape
-        with torch.cuda.device_of(xyz1):
-            code = _lib.lib().sn_emd_backward(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), _lib.fptr(graddist, "graddist"),
-                _lib.iptr(assignment, "assignment"), b, n, _lib.fptr(gradxyz1, "gradxyz1"),
-                _lib.stream_of(xyz1))
-        _lib.check(code, "sn_emd_backward")
+        _lib.call("sn_emd_backward", xyz1, xyz2, graddist, assignment, b, n, gradxyz1)
         return gradxyz1, gradxyz2, None, None
 
 

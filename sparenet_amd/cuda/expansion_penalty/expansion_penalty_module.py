@@ -7,8 +7,6 @@ forward(input [B,n,3], primitive_size, alpha) ->
 GPU tensors only.  Backed by sn_expansion_forward / sn_expansion_backward; the
 reference's two [B, n*512] neighbor/cost scratch tensors (:33-34) do not exist.
 """
-import ctypes
-
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -27,15 +25,9 @@ class expansionPenaltyFunction(Function):
         dist = torch.empty(batchsize, n, device=dev)
         assignment = torch.empty(batchsize, n, device=dev, dtype=torch.int32)
         mean_mst_length = torch.empty(batchsize, device=dev)
-        with torch.cuda.device_of(xyz):
-            nbytes = _lib.lib().sn_expansion_workspace_bytes(batchsize, n, int(primitive_size))
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            code = _lib.lib().sn_expansion_forward(
-                _lib.fptr(xyz, "xyz"), batchsize, n, int(primitive_size), _lib.cfloat(alpha),
-                _lib.fptr(dist, "dist"), _lib.iptr(assignment, "assignment"),
-                _lib.fptr(mean_mst_length, "mean_mst_length"), ctypes.c_void_p(ws.data_ptr()),
-                ctypes.c_size_t(nbytes), _lib.stream_of(xyz))
-        _lib.check(code, "sn_expansion_forward")
+        ws = _lib.workspace("sn_expansion_workspace_bytes", xyz, batchsize, n, primitive_size)
+        _lib.call("sn_expansion_forward", xyz, batchsize, n, primitive_size, alpha, dist, assignment,
+                  mean_mst_length, ws)
         ctx.save_for_backward(xyz, assignment)
         ctx.mark_non_differentiable(assignment)
         return dist, assignment, mean_mst_length / (n / primitive_size)
@@ -48,12 +40,7 @@ class expansionPenaltyFunction(Function):
         grad_dist = grad_dist.contiguous().float()
         b, n, _ = xyz.shape
         grad_xyz = torch.empty_like(xyz)
-        with torch.cuda.device_of(xyz):
-            code = _lib.lib().sn_expansion_backward(
-                _lib.fptr(xyz, "xyz"), _lib.fptr(grad_dist, "grad_dist"),
-                _lib.iptr(assignment, "assignment"), b, n, _lib.fptr(grad_xyz, "grad_xyz"),
-                _lib.stream_of(xyz))
-        _lib.check(code, "sn_expansion_backward")
+        _lib.call("sn_expansion_backward", xyz, grad_dist, assignment, b, n, grad_xyz)
         return grad_xyz, None, None
 
 

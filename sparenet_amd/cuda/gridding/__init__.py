@@ -25,13 +25,10 @@ class GriddingFunction(torch.autograd.Function):
         grid = torch.empty(b, full ** 3, device=dev)
         weights = torch.empty(b, n, 8, 3, device=dev)
         indexes = torch.empty(b, n, 8, dtype=torch.int32, device=dev)
-        with torch.cuda.device_of(ptcloud):
-            fn = _lib.lib().sn_gridding_forward_padded if skip_padding else _lib.lib().sn_gridding_forward
-            code = fn(
-                _lib.fptr(ptcloud, "ptcloud"), b, n, full, _lib.fptr(grid, "grid"),
-                _lib.fptr(weights, "grid_pt_weights"), _lib.iptr(indexes, "grid_pt_indexes"),
-                _lib.stream_of(ptcloud))
-        _lib.check(code, "sn_gridding_forward")
+        if skip_padding:
+            _lib.call("sn_gridding_forward_padded", ptcloud, b, n, full, grid, weights, indexes)
+        else:
+            _lib.call("sn_gridding_forward", ptcloud, b, n, full, grid, weights, indexes)
         ctx.save_for_backward(weights, indexes)
         return grid
 
@@ -41,12 +38,7 @@ class GriddingFunction(torch.autograd.Function):
         grad_grid = grad_grid.contiguous().float()
         b, n = indexes.shape[:2]
         grad_ptcloud = torch.empty(b, n, 3, device=grad_grid.device)
-        with torch.cuda.device_of(grad_grid):
-            code = _lib.lib().sn_gridding_backward(
-                _lib.fptr(grad_grid, "grad_grid"), _lib.fptr(weights, "grid_pt_weights"),
-                _lib.iptr(indexes, "grid_pt_indexes"), b, n, grad_grid.size(1),
-                _lib.fptr(grad_ptcloud, "grad_ptcloud"), _lib.stream_of(grad_grid))
-        _lib.check(code, "sn_gridding_backward")
+        _lib.call("sn_gridding_backward", grad_grid, weights, indexes, b, n, grad_grid.size(1), grad_ptcloud)
         return None, grad_ptcloud, None
 
 
@@ -70,11 +62,7 @@ class GriddingReverseFunction(torch.autograd.Function):
         grid = grid.contiguous().float()
         b = grid.size(0)
         ptcloud = torch.empty(b, scale ** 3, 3, device=grid.device)
-        with torch.cuda.device_of(grid):
-            code = _lib.lib().sn_gridding_reverse_forward(
-                _lib.fptr(grid, "grid"), b, int(scale), _lib.fptr(ptcloud, "ptcloud"),
-                _lib.stream_of(grid))
-        _lib.check(code, "sn_gridding_reverse_forward")
+        _lib.call("sn_gridding_reverse_forward", grid, b, scale, ptcloud)
         ctx.scale = int(scale)
         ctx.save_for_backward(grid, ptcloud)
         return ptcloud
@@ -86,12 +74,7 @@ class GriddingReverseFunction(torch.autograd.Function):
         grad_ptcloud = grad_ptcloud.contiguous().float()
         b = grid.size(0)
         grad_grid = torch.empty(b, scale ** 3, device=grid.device)
-        with torch.cuda.device_of(grid):
-            code = _lib.lib().sn_gridding_reverse_backward(
-                _lib.fptr(grad_ptcloud, "grad_ptcloud"), _lib.fptr(grid, "grid"),
-                _lib.fptr(ptcloud, "ptcloud"), b, scale, _lib.fptr(grad_grid, "grad_grid"),
-                _lib.stream_of(grid))
-        _lib.check(code, "sn_gridding_reverse_backward")
+        _lib.call("sn_gridding_reverse_backward", grad_ptcloud, grid, ptcloud, b, scale, grad_grid)
         return None, grad_grid.view(-1, scale, scale, scale)
 
 

@@ -20,12 +20,7 @@ def _grid_one(cloud, bounds):
     grid = torch.empty(b, nverts, 8, device=dev)
     weights = torch.empty(b, n, 8, 3, device=dev)
     indexes = torch.empty(b, n, 8, dtype=torch.int32, device=dev)
-    with torch.cuda.device_of(cloud):
-        code = _lib.lib().sn_gridding_dist_forward(
-            _lib.fptr(cloud, "ptcloud"), b, n, mnx, mxx, mny, mxy, mnz, mxz, _lib.fptr(grid, "grid"),
-            _lib.fptr(weights, "grid_pt_weights"), _lib.iptr(indexes, "grid_pt_indexes"),
-            _lib.stream_of(cloud))
-    _lib.check(code, "sn_gridding_dist_forward")
+    _lib.call("sn_gridding_dist_forward", cloud, b, n, mnx, mxx, mny, mxy, mnz, mxz, grid, weights, indexes)
     return grid, weights, indexes
 
 
@@ -33,12 +28,8 @@ def _grad_one(grad_grid, weights, indexes):
     grad_grid = grad_grid.contiguous().float()
     b, n = indexes.shape[:2]
     grad_cloud = torch.empty(b, n, 3, device=grad_grid.device)
-    with torch.cuda.device_of(grad_grid):
-        code = _lib.lib().sn_gridding_backward(
-            _lib.fptr(grad_grid, "grad_grid"), _lib.fptr(weights, "grid_pt_weights"),
-            _lib.iptr(indexes, "grid_pt_indexes"), b, n, grad_grid.size(1) * grad_grid.size(2),
-            _lib.fptr(grad_cloud, "grad_ptcloud"), _lib.stream_of(grad_grid))
-    _lib.check(code, "sn_gridding_backward")
+    _lib.call("sn_gridding_backward", grad_grid, weights, indexes, b, n, grad_grid.size(1) * grad_grid.size(2),
+              grad_cloud)
     return grad_cloud
 
 

@@ -9,8 +9,6 @@ no [B,N,N] matrix in HBM); wider features or larger k take the inner products fr
 and ranks them with sn_knn_topk.  Neighbours come out ascending by distance, the point itself first,
 equal scores by lower index.
 """
-import ctypes
-
 import torch
 
 from sparenet_amd import _lib
@@ -31,12 +29,7 @@ def knn_fused(x, k: int):
     x = x.contiguous().float()
     b, c, n = x.shape
     idx = torch.empty(b, n, k, dtype=torch.int64, device=x.device)
-    with torch.cuda.device_of(x):
-        nbytes = _lib.lib().sn_knn_workspace_bytes(b, n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        code = _lib.lib().sn_knn(_lib.fptr(x, "x"), b, c, n, int(k), ctypes.c_void_p(idx.data_ptr()),
-                                 ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes), _lib.stream_of(x))
-    _lib.check(code, "sn_knn")
+    _lib.call("sn_knn", x, b, c, n, k, idx, _lib.workspace("sn_knn_workspace_bytes", x, b, n))
     return idx
 
 
@@ -47,10 +40,7 @@ def knn_unfused(x, k: int):
     inner = torch.bmm(x.transpose(2, 1), x).contiguous()        # [B, N, N]
     xx = (x * x).sum(dim=1).contiguous()                        # [B, N]
     idx = torch.empty(b, n, k, dtype=torch.int64, device=x.device)
-    with torch.cuda.device_of(x):
-        code = _lib.lib().sn_knn_topk(_lib.fptr(inner, "inner"), _lib.fptr(xx, "xx"), b, n, int(k),
-                                      ctypes.c_void_p(idx.data_ptr()), _lib.stream_of(x))
-    _lib.check(code, "sn_knn_topk")
+    _lib.call("sn_knn_topk", inner, xx, b, n, k, idx)
     return idx
 
 
@@ -62,11 +52,7 @@ class GraphFeatureFunction(torch.autograd.Function):
         b, c, n = x.shape
         k = idx.size(2)
         out = torch.empty(b, 2 * c, n, k, device=x.device)
-        with torch.cuda.device_of(x):
-            code = _lib.lib().sn_graph_feature_forward(
-                _lib.fptr(x, "x"), ctypes.c_void_p(idx.data_ptr()), b, c, n, k, _lib.fptr(out, "out"),
-                _lib.stream_of(x))
-        _lib.check(code, "sn_graph_feature_forward")
+        _lib.call("sn_graph_feature_forward", x, idx, b, c, n, k, out)
         ctx.save_for_backward(idx)
         ctx.shape = (b, c, n, k)
         return out
@@ -77,14 +63,8 @@ class GraphFeatureFunction(torch.autograd.Function):
         b, c, n, k = ctx.shape
         grad_out = grad_out.contiguous().float()
         grad_x = torch.empty(b, c, n, device=grad_out.device)
-        with torch.cuda.device_of(grad_out):
-            nbytes = _lib.lib().sn_graph_feature_backward_workspace_bytes(b, n, k)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_out.device)
-            code = _lib.lib().sn_graph_feature_backward(
-                _lib.fptr(grad_out, "grad_out"), ctypes.c_void_p(idx.data_ptr()), b, c, n, k,
-                _lib.fptr(grad_x, "grad_x"), ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes),
-                _lib.stream_of(grad_out))
-        _lib.check(code, "sn_graph_feature_backward")
+        ws = _lib.workspace("sn_graph_feature_backward_workspace_bytes", grad_out, b, n, k)
+        _lib.call("sn_graph_feature_backward", grad_out, idx, b, c, n, k, grad_x, ws)
         return grad_x, None
 
 

@@ -28,7 +28,8 @@ def _shapes(points, point_features, background):
 
 
 class _Ext:
-    """Stand-in for the reference's JIT-built `ext` module (cuda/p2i_op/ext.cpp:5-15)."""
+    """Stand-in for the reference's JIT-built `ext` module (cuda/p2i_op/ext.cpp:5-15).  float64 tensors take the
+    `_f64` entry points; the declared pointee types make `_lib.call` check every tensor against the one chosen."""
 
     @staticmethod
     def p2i_max_forward_gpu(points, point_features, batch_inds, background, kernel_kind,
@@ -38,28 +39,11 @@ class _Ext:
         n, c, b, h, w = _shapes(points, point_features, background)
         out = torch.empty_like(background)
         ids = torch.empty(background.shape, dtype=torch.int32, device=background.device)
-        if points.dtype == torch.float64:
-            with torch.cuda.device_of(background):
-                nbytes = _lib.lib().sn_p2i_f64_workspace_bytes(b, c, h, w)
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=background.device)
-                code = _lib.lib().sn_p2i_max_forward_f64(
-                    _lib.dptr(points, "points"), _lib.dptr(point_features, "point_features"),
-                    _lib.iptr(batch_inds, "batch_inds"), _lib.dptr(background, "background"),
-                    n, c, b, h, w, ctypes.c_double(kernel_radius), _lib.dptr(out, "out"),
-                    _lib.iptr(ids, "out_point_ids"), ctypes.c_void_p(ws.data_ptr()),
-                    ctypes.c_size_t(nbytes), _lib.stream_of(background))
-            _lib.check(code, "sn_p2i_max_forward_f64")
-            return out, ids
-        with torch.cuda.device_of(background):
-            nbytes = _lib.lib().sn_p2i_max_workspace_bytes(b, c, h, w)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=background.device)
-            code = _lib.lib().sn_p2i_max_forward(
-                _lib.fptr(points, "points"), _lib.fptr(point_features, "point_features"),
-                _lib.iptr(batch_inds, "batch_inds"), _lib.fptr(background, "background"),
-                n, c, b, h, w, _lib.cfloat(kernel_radius), _lib.fptr(out, "out"),
-                _lib.iptr(ids, "out_point_ids"), ctypes.c_void_p(ws.data_ptr()),
-                ctypes.c_size_t(nbytes), _lib.stream_of(background))
-        _lib.check(code, "sn_p2i_max_forward")
+        f64 = points.dtype == torch.float64
+        ws = _lib.workspace("sn_p2i_f64_workspace_bytes" if f64 else "sn_p2i_max_workspace_bytes", background,
+                            b, c, h, w)
+        _lib.call("sn_p2i_max_forward_f64" if f64 else "sn_p2i_max_forward", points, point_features, batch_inds,
+                  background, n, c, b, h, w, kernel_radius, out, ids, ws)
         return out, ids
 
     @staticmethod
@@ -80,17 +64,9 @@ class _Ext:
         host_radii = (ctypes.c_float * nr)(*[float(r) for r in radii])
         if zero_bg and max(float(r) for r in radii) > 16.0:
             background, zero_bg = torch.zeros(b, c, h, w, dtype=points.dtype, device=points.device), False
-        with torch.cuda.device_of(points):
-            nbytes = _lib.lib().sn_p2i_max_multi_workspace_bytes(n, b, c, h, w)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
-            code = _lib.lib().sn_p2i_max_forward_multi(
-                _lib.fptr(points, "points"), _lib.fptr(point_features, "point_features"),
-                _lib.iptr(batch_inds, "batch_inds"),
-                ctypes.c_void_p(0) if zero_bg else _lib.fptr(background, "background"),
-                n, c, b, h, w, host_radii, nr, int(bool(image_major)), _lib.fptr(out, "out"),
-                _lib.iptr(ids, "out_point_ids"), ctypes.c_void_p(ws.data_ptr()),
-                ctypes.c_size_t(nbytes), _lib.stream_of(points))
-        _lib.check(code, "sn_p2i_max_forward_multi")
+        ws = _lib.workspace("sn_p2i_max_multi_workspace_bytes", points, n, b, c, h, w)
+        _lib.call("sn_p2i_max_forward_multi", points, point_features, batch_inds, None if zero_bg else background,
+                  n, c, b, h, w, host_radii, nr, bool(image_major), out, ids, ws)
         return out, ids
 
     @staticmethod
@@ -102,27 +78,13 @@ class _Ext:
         points_grad = torch.empty_like(points)
         feat_grad = torch.empty_like(point_features)
         bg_grad = torch.empty_like(out_grad)
-        if points.dtype == torch.float64:
-            with torch.cuda.device_of(out_grad):
-                code = _lib.lib().sn_p2i_max_backward_f64(
-                    _lib.dptr(out_grad, "out_grad"), _lib.iptr(out_point_ids, "out_point_ids"),
-                    _lib.dptr(points, "points"), _lib.dptr(point_features, "point_features"),
-                    n, c, b, h, w, ctypes.c_double(kernel_radius), _lib.dptr(points_grad, "points_grad"),
-                    _lib.dptr(feat_grad, "point_features_grad"), _lib.dptr(bg_grad, "background_grad"),
-                    _lib.stream_of(out_grad))
-            _lib.check(code, "sn_p2i_max_backward_f64")
-            return points_grad, feat_grad, bg_grad
-        with torch.cuda.device_of(out_grad):
-            nbytes = _lib.lib().sn_p2i_max_backward_workspace_bytes(b, c, h, w)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=out_grad.device)
-            code = _lib.lib().sn_p2i_max_backward(
-                _lib.fptr(out_grad, "out_grad"), _lib.iptr(out_point_ids, "out_point_ids"),
-                _lib.fptr(points, "points"), _lib.fptr(point_features, "point_features"),
-                _lib.iptr(batch_inds, "batch_inds") if batch_inds is not None else ctypes.c_void_p(0),
-                n, c, b, h, w, _lib.cfloat(kernel_radius), _lib.fptr(points_grad, "points_grad"),
-                _lib.fptr(feat_grad, "point_features_grad"), _lib.fptr(bg_grad, "background_grad"),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes), _lib.stream_of(out_grad))
-        _lib.check(code, "sn_p2i_max_backward")
+        if points.dtype == torch.float64:      # the float64 entry point takes neither batch_inds nor a workspace
+            _lib.call("sn_p2i_max_backward_f64", out_grad, out_point_ids, points, point_features, n, c, b, h, w,
+                      kernel_radius, points_grad, feat_grad, bg_grad)
+        else:
+            ws = _lib.workspace("sn_p2i_max_backward_workspace_bytes", out_grad, b, c, h, w)
+            _lib.call("sn_p2i_max_backward", out_grad, out_point_ids, points, point_features, batch_inds, n, c, b, h,
+                      w, kernel_radius, points_grad, feat_grad, bg_grad, ws)
         return points_grad, feat_grad, bg_grad
 
     @staticmethod
@@ -140,19 +102,11 @@ class _Ext:
         points_grad = torch.empty_like(points)
         feat_grad = torch.empty_like(point_features)
         bg_grad = (torch.empty((b, c, h, w), dtype=out_grad.dtype, device=out_grad.device)
-                   if want_background_grad else None)
+                   if want_background_grad else None)      # None: a null pointer, the gradient is not computed
         host_radii = (ctypes.c_float * nr)(*[float(r) for r in radii])
-        with torch.cuda.device_of(out_grad):
-            nbytes = _lib.lib().sn_p2i_max_backward_multi_workspace_bytes(n, c)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=out_grad.device)
-            code = _lib.lib().sn_p2i_max_backward_multi(
-                _lib.fptr(out_grad, "out_grad"), _lib.iptr(out_point_ids, "out_point_ids"),
-                _lib.fptr(points, "points"), _lib.fptr(point_features, "point_features"),
-                n, c, b, h, w, host_radii, nr, int(bool(image_major)), _lib.fptr(points_grad, "points_grad"),
-                _lib.fptr(feat_grad, "point_features_grad"),
-                _lib.fptr(bg_grad, "background_grad") if want_background_grad else ctypes.c_void_p(0),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes), _lib.stream_of(out_grad))
-        _lib.check(code, "sn_p2i_max_backward_multi")
+        ws = _lib.workspace("sn_p2i_max_backward_multi_workspace_bytes", out_grad, n, c)
+        _lib.call("sn_p2i_max_backward_multi", out_grad, out_point_ids, points, point_features, n, c, b, h, w,
+                  host_radii, nr, bool(image_major), points_grad, feat_grad, bg_grad, ws)
         return points_grad, feat_grad, bg_grad
 
     @staticmethod
@@ -162,20 +116,8 @@ class _Ext:
             raise ValueError("p2i: only kernel_kind 0 ('cos') exists")
         n, c, b, h, w = _shapes(points, point_features, background)
         out = background.clone()
-        if points.dtype == torch.float64:
-            with torch.cuda.device_of(background):
-                code = _lib.lib().sn_p2i_sum_forward_f64(
-                    _lib.dptr(points, "points"), _lib.dptr(point_features, "point_features"),
-                    _lib.iptr(batch_inds, "batch_inds"), n, c, b, h, w, ctypes.c_double(kernel_radius),
-                    _lib.dptr(out, "out"), _lib.stream_of(background))
-            _lib.check(code, "sn_p2i_sum_forward_f64")
-            return out
-        with torch.cuda.device_of(background):
-            code = _lib.lib().sn_p2i_sum_forward(
-                _lib.fptr(points, "points"), _lib.fptr(point_features, "point_features"),
-                _lib.iptr(batch_inds, "batch_inds"), n, c, b, h, w, _lib.cfloat(kernel_radius),
-                _lib.fptr(out, "out"), _lib.stream_of(background))
-        _lib.check(code, "sn_p2i_sum_forward")
+        _lib.call("sn_p2i_sum_forward_f64" if points.dtype == torch.float64 else "sn_p2i_sum_forward", points,
+                  point_features, batch_inds, n, c, b, h, w, kernel_radius, out)
         return out
 
     @staticmethod
@@ -186,22 +128,8 @@ class _Ext:
         b, _, h, w = out_grad.shape
         points_grad = torch.empty_like(points)
         feat_grad = torch.empty_like(point_features)
-        if points.dtype == torch.float64:
-            with torch.cuda.device_of(out_grad):
-                code = _lib.lib().sn_p2i_sum_backward_f64(
-                    _lib.dptr(out_grad, "out_grad"), _lib.dptr(points, "points"),
-                    _lib.dptr(point_features, "point_features"), _lib.iptr(batch_inds, "batch_inds"),
-                    n, c, b, h, w, ctypes.c_double(kernel_radius), _lib.dptr(points_grad, "points_grad"),
-                    _lib.dptr(feat_grad, "point_features_grad"), _lib.stream_of(out_grad))
-            _lib.check(code, "sn_p2i_sum_backward_f64")
-            return points_grad, feat_grad
-        with torch.cuda.device_of(out_grad):
-            code = _lib.lib().sn_p2i_sum_backward(
-                _lib.fptr(out_grad, "out_grad"), _lib.fptr(points, "points"),
-                _lib.fptr(point_features, "point_features"), _lib.iptr(batch_inds, "batch_inds"),
-                n, c, b, h, w, _lib.cfloat(kernel_radius), _lib.fptr(points_grad, "points_grad"),
-                _lib.fptr(feat_grad, "point_features_grad"), _lib.stream_of(out_grad))
-        _lib.check(code, "sn_p2i_sum_backward")
+        _lib.call("sn_p2i_sum_backward_f64" if points.dtype == torch.float64 else "sn_p2i_sum_backward", out_grad,
+                  points, point_features, batch_inds, n, c, b, h, w, kernel_radius, points_grad, feat_grad)
         return points_grad, feat_grad
 
 

@@ -14,8 +14,6 @@ dense op gives for that cloud alone, bit for bit, whatever else is in the batch.
 tensor is used as it is, without a host read (the kernels hold its values to [0, N]).  CPU clouds are accepted by
 chamfer_ragged only, as by the dense ops: it loops over the clouds through the library's host Chamfer.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -53,10 +51,6 @@ def _check_pair(what, xyz1, xyz2):
         raise ValueError(f"{what}: xyz1 and xyz2 are on different devices")
 
 
-def _void(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 # ---------------------------------------------------------------------------------------------------- pad_compact
 class PadCompactFunction(Function):
     @staticmethod
@@ -68,10 +62,7 @@ class PadCompactFunction(Function):
         packed = torch.empty_like(xyz)
         lengths = torch.empty(b, dtype=torch.int32, device=xyz.device)
         src = torch.empty(b, n, dtype=torch.int32, device=xyz.device)
-        with torch.cuda.device_of(xyz):
-            code = _lib.lib().sn_pad_compact(_lib.fptr(xyz, "xyz"), b, n, _lib.fptr(packed, "packed"),
-                                             _lib.iptr(lengths, "lengths"), _lib.iptr(src, "src"), _lib.stream_of(xyz))
-        _lib.check(code, "sn_pad_compact")
+        _lib.call("sn_pad_compact", xyz, b, n, packed, lengths, src)
         ctx.save_for_backward(src)
         ctx.mark_non_differentiable(lengths, src)
         return packed, lengths, src
@@ -87,10 +78,7 @@ def scatter_rows(rows, src):
     b, n = src.shape
     c = rows.numel() // (b * n)
     out = torch.empty_like(rows)
-    with torch.cuda.device_of(rows):
-        code = _lib.lib().sn_pad_scatter_rows(_lib.fptr(rows, "rows"), _lib.iptr(src, "src"), b, n, c,
-                                              _lib.fptr(out, "out"), _lib.stream_of(rows))
-    _lib.check(code, "sn_pad_scatter_rows")
+    _lib.call("sn_pad_scatter_rows", rows, src, b, n, c, out)
     return out
 
 
@@ -144,12 +132,7 @@ def chamfer_ragged_forward_raw(xyz1, xyz2, lengths1, lengths2):
     if not xyz1.is_cuda:
         _chamfer_host(xyz1, xyz2, h1, h2, dist1, dist2, idx1, idx2)
     else:
-        with torch.cuda.device_of(xyz1):
-            code = _lib.lib().sn_chamfer_forward_ragged(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), b, n, m, _lib.iptr(l1, "lengths1"),
-                _lib.iptr(l2, "lengths2"), _lib.fptr(dist1, "dist1"), _lib.iptr(idx1, "idx1"),
-                _lib.fptr(dist2, "dist2"), _lib.iptr(idx2, "idx2"), _lib.stream_of(xyz1))
-        _lib.check(code, "sn_chamfer_forward_ragged")
+        _lib.call("sn_chamfer_forward_ragged", xyz1, xyz2, b, n, m, l1, l2, dist1, idx1, dist2, idx2)
     return dist1, dist2, idx1, idx2, xyz1, xyz2, l1, l2
 
 
@@ -173,15 +156,9 @@ class ChamferRaggedFunction(Function):
             _chamfer_host_backward(xyz1, xyz2, l1.tolist(), l2.tolist(), graddist1, graddist2, idx1, idx2,
                                    gradxyz1, gradxyz2)
             return gradxyz1, gradxyz2, None, None
-        with torch.cuda.device_of(xyz1):
-            nbytes = _lib.lib().sn_chamfer_backward_ragged_workspace_bytes(b, n, m)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz1.device)
-            code = _lib.lib().sn_chamfer_backward_ragged(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), _lib.fptr(graddist1, "graddist1"),
-                _lib.fptr(graddist2, "graddist2"), _lib.iptr(idx1, "idx1"), _lib.iptr(idx2, "idx2"), b, n, m,
-                _lib.iptr(l1, "lengths1"), _lib.iptr(l2, "lengths2"), _lib.fptr(gradxyz1, "gradxyz1"),
-                _lib.fptr(gradxyz2, "gradxyz2"), _void(ws), ctypes.c_size_t(nbytes), _lib.stream_of(xyz1))
-        _lib.check(code, "sn_chamfer_backward_ragged")
+        ws = _lib.workspace("sn_chamfer_backward_ragged_workspace_bytes", xyz1, b, n, m)
+        _lib.call("sn_chamfer_backward_ragged", xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m, l1, l2,
+                  gradxyz1, gradxyz2, ws)
         return gradxyz1, gradxyz2, None, None
 
 
@@ -202,20 +179,13 @@ class EmdRaggedFunction(Function):
         b, n, _ = xyz1.shape
         m = xyz2.size(1)
         dev = xyz1.device
-        _lib.fptr(xyz1, "xyz1")      # CPU tensors are refused before anything is uploaded
+        _lib.require_device(xyz1, "xyz1")      # CPU tensors are refused before anything is uploaded
         l1, h1 = device_lengths(lengths1, b, n, dev, "lengths1")
         l2, h2 = device_lengths(lengths2, b, m, dev, "lengths2")
         dist = torch.empty(b, n, device=dev)
         assignment = torch.empty(b, n, device=dev, dtype=torch.int32)
-        with torch.cuda.device_of(xyz1):
-            nbytes = _lib.lib().sn_emd_ragged_workspace_bytes(b, n, m)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            code = _lib.lib().sn_emd_forward_ragged(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), b, n, m, _lib.iptr(l1, "lengths1"),
-                _lib.iptr(l2, "lengths2"), _lib.cfloat(eps), int(iters), _lib.fptr(dist, "dist"),
-                _lib.iptr(assignment, "assignment"), _void(ws), ctypes.c_size_t(nbytes), ctypes.c_void_p(0),
-                _lib.stream_of(xyz1))
-        _lib.check(code, "sn_emd_forward_ragged")
+        ws = _lib.workspace("sn_emd_ragged_workspace_bytes", xyz1, b, n, m)
+        _lib.call("sn_emd_forward_ragged", xyz1, xyz2, b, n, m, l1, l2, eps, iters, dist, assignment, ws, None)
         ctx.save_for_backward(xyz1, xyz2, assignment, l1, l2)
         ctx.mark_non_differentiable(assignment)
         return dist, assignment
@@ -229,15 +199,9 @@ class EmdRaggedFunction(Function):
         need2 = ctx.needs_input_grad[1]
         gradxyz1 = torch.empty_like(xyz1)
         gradxyz2 = torch.empty_like(xyz2) if need2 else None
-        with torch.cuda.device_of(xyz1):
-            nbytes = _lib.lib().sn_emd_ragged_backward_workspace_bytes(b, n, m) if need2 else 0
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=xyz1.device)
-            code = _lib.lib().sn_emd_backward_ragged(
-                _lib.fptr(xyz1, "xyz1"), _lib.fptr(xyz2, "xyz2"), _lib.fptr(graddist, "graddist"),
-                _lib.iptr(assignment, "assignment"), b, n, m, _lib.iptr(l1, "lengths1"), _lib.iptr(l2, "lengths2"),
-                _lib.fptr(gradxyz1, "gradxyz1"), _lib.fptr(gradxyz2, "gradxyz2") if need2 else ctypes.c_void_p(0),
-                _void(ws), ctypes.c_size_t(nbytes), _lib.stream_of(xyz1))
-        _lib.check(code, "sn_emd_backward_ragged")
+        # without gradxyz2 (None: a null pointer) the library needs no workspace either
+        ws = _lib.workspace("sn_emd_ragged_backward_workspace_bytes", xyz1, b, n, m) if need2 else None
+        _lib.call("sn_emd_backward_ragged", xyz1, xyz2, graddist, assignment, b, n, m, l1, l2, gradxyz1, gradxyz2, ws)
         return gradxyz1, gradxyz2, None, None, None, None
 
 

@@ -118,12 +118,7 @@ class DepthProjectFunction(torch.autograd.Function):
         zminmax = torch.empty(2, dtype=torch.int32, device=dev)
         mat = (ctypes.c_float * 16)(*matrix16)
         extent = float(image_size - 1)
-        with torch.cuda.device_of(pts):
-            code = _lib.lib().sn_depth_project_forward(
-                _lib.fptr(pts, "data"), ctypes.c_long(n), mat, _lib.cfloat(extent),
-                _lib.fptr(pixel, "pixel"), _lib.fptr(z, "z"), ctypes.c_void_p(zminmax.data_ptr()),
-                _lib.fptr(feat, "feat"), _lib.stream_of(pts))
-        _lib.check(code, "sn_depth_project_forward")
+        _lib.call("sn_depth_project_forward", pts, n, mat, extent, pixel, z, zminmax, feat)
         ctx.save_for_backward(pts, z, zminmax)
         ctx.mat, ctx.extent, ctx.shape = mat, extent, data.shape
         return pixel, feat
@@ -136,15 +131,7 @@ class DepthProjectFunction(torch.autograd.Function):
         ws = torch.empty(32, dtype=torch.uint8, device=pts.device)
         gp = g_pixel.contiguous().float() if g_pixel is not None else None
         gf = g_feat.contiguous().float() if g_feat is not None else None
-        null = ctypes.c_void_p(0)
-        with torch.cuda.device_of(pts):
-            code = _lib.lib().sn_depth_project_backward(
-                _lib.fptr(pts, "data"), ctypes.c_long(n), ctx.mat, _lib.cfloat(ctx.extent),
-                _lib.fptr(z, "z"), ctypes.c_void_p(zminmax.data_ptr()),
-                _lib.fptr(gp, "g_pixel") if gp is not None else null,
-                _lib.fptr(gf, "g_feat") if gf is not None else null,
-                ctypes.c_void_p(ws.data_ptr()), _lib.fptr(g_data, "g_data"), _lib.stream_of(pts))
-        _lib.check(code, "sn_depth_project_backward")
+        _lib.call("sn_depth_project_backward", pts, n, ctx.mat, ctx.extent, z, zminmax, gp, gf, ws, g_data)
         return g_data.view(ctx.shape), None, None
 
 
@@ -164,12 +151,7 @@ class DepthProjectViewsFunction(torch.autograd.Function):
         zminmax = torch.empty(2 * v, dtype=torch.int32, device=dev)
         mat = (ctypes.c_float * (16 * v))(*[x for m in matrices for x in m])
         extent = float(image_size - 1)
-        with torch.cuda.device_of(pts):
-            code = _lib.lib().sn_depth_project_forward_views(
-                _lib.fptr(pts, "data"), ctypes.c_long(n), mat, v, _lib.cfloat(extent),
-                _lib.fptr(pixel, "pixel"), _lib.fptr(z, "z"), ctypes.c_void_p(zminmax.data_ptr()),
-                _lib.fptr(feat, "feat"), _lib.stream_of(pts))
-        _lib.check(code, "sn_depth_project_forward_views")
+        _lib.call("sn_depth_project_forward_views", pts, n, mat, v, extent, pixel, z, zminmax, feat)
         ctx.save_for_backward(pts, z, zminmax)
         ctx.mat, ctx.nviews, ctx.extent, ctx.shape = mat, v, extent, data.shape
         return pixel, feat
@@ -182,15 +164,8 @@ class DepthProjectViewsFunction(torch.autograd.Function):
         ws = torch.empty(32 * ctx.nviews, dtype=torch.uint8, device=pts.device)
         gp = g_pixel.contiguous().float() if g_pixel is not None else None
         gf = g_feat.contiguous().float() if g_feat is not None else None
-        null = ctypes.c_void_p(0)
-        with torch.cuda.device_of(pts):
-            code = _lib.lib().sn_depth_project_backward_views(
-                _lib.fptr(pts, "data"), ctypes.c_long(n), ctx.mat, ctx.nviews, _lib.cfloat(ctx.extent),
-                _lib.fptr(z, "z"), ctypes.c_void_p(zminmax.data_ptr()),
-                _lib.fptr(gp, "g_pixel") if gp is not None else null,
-                _lib.fptr(gf, "g_feat") if gf is not None else null,
-                ctypes.c_void_p(ws.data_ptr()), _lib.fptr(g_data, "g_data"), _lib.stream_of(pts))
-        _lib.check(code, "sn_depth_project_backward_views")
+        _lib.call("sn_depth_project_backward_views", pts, n, ctx.mat, ctx.nviews, ctx.extent, z, zminmax, gp, gf, ws,
+                  g_data)
         return g_data.view(ctx.shape), None, None
 
 

@@ -111,30 +111,48 @@ def _split_top_level(argtext):
     return parts
 
 
-def _call_sites(src, name):
-    """Argument counts of every `name(` call in a Python source text."""
-    counts = []
-    for m in re.finditer(re.escape(name) + r"\s*\(", src):
+def _call_sites(src, opening):
+    """Argument texts (split at top-level commas) of every call in a Python source text whose text up to and
+    including the opening parenthesis matches the regular expression `opening`."""
+    sites = []
+    for m in re.finditer(opening, src):
         i, depth = m.end(), 1
         while depth and i < len(src):
             depth += src[i] in "([{"
             depth -= src[i] in ")]}"
             i += 1
-        counts.append(len(_split_top_level(src[m.end():i - 1])))
-    return counts
+        sites.append(_split_top_level(src[m.end():i - 1]))
+    return sites
+
+
+def _package_sources():
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "sparenet_amd")):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                yield os.path.join(dirpath, f), open(os.path.join(dirpath, f)).read()
+
+
+PARENT_CHECKED = 104    # call sites this test counted before the package moved onto _lib.call (70 + 21 + 13)
 
 
 def test_every_python_call_passes_the_declared_number_of_arguments():
     """ctypes does not check argument counts: a parameter added to the C entry point and forgotten at a call site
-    shifts every later argument silently.  Every `sn_*(...)` call in the package, bench.py and tools/ is counted
-    against the prototype in include/sparenet_hip.h."""
+    shifts every later argument silently.  Every direct `.sn_*(...)` call in the package, bench.py and tools/ is
+    counted against the prototype in include/sparenet_hip.h, and so is every `call("sn_*", ...)` /
+    `workspace("sn_*", like, ...)` of the package against what _lib.call takes for that prototype: the declared
+    parameters without the trailing stream and without a workspace_bytes that follows a workspace."""
     hdr = open(os.path.join(ROOT, "include", "sparenet_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    protos = {}
+    protos, through_call = {}, {}
     for m in re.finditer(r"^(?:int|size_t|void|long long|const char \*)\s*(sn_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", hdr,
                          re.M | re.S):
         args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args in ("", "void") else len(_split_top_level(args))
+        names = [] if args in ("", "void") else [re.findall(r"\w+", a)[-1] for a in _split_top_level(args)]
+        protos[m.group(1)] = len(names)
+        if names and names[-1] == "stream":
+            names.pop()
+        through_call[m.group(1)] = len(names) - sum(a == "workspace" and b == "workspace_bytes"
+                                                    for a, b in zip(names, names[1:]))
     assert len(protos) >= 40
     checked = 0
     for base in ("sparenet_amd", "tools", "."):
@@ -145,11 +163,37 @@ def test_every_python_call_passes_the_declared_number_of_arguments():
                     continue
                 src = open(os.path.join(dirpath, f)).read()
                 for name, want in protos.items():
-                    for got in _call_sites(src, "." + name):
+                    for args in _call_sites(src, re.escape("." + name) + r"\s*\("):
                         # attribute access like `.sn_x.restype = ...` is not a call and is not matched (needs "(")
-                        assert got == want, f"{os.path.join(dirpath, f)}: {name} called with {got} arguments, declared {want}"
+                        assert len(args) == want, f"{os.path.join(dirpath, f)}: {name} called with {len(args)} arguments, declared {want}"
                         checked += 1
-    assert checked >= 40
+    for path, src in _package_sources():
+        if path.endswith("_lib.py"):
+            continue
+        # `workspace(export, like, *shape)` hands the shape to call(export, ...): one argument more than call takes
+        for helper, extra in (("call", 0), ("workspace", 1)):
+            for args in _call_sites(src, r"(?:\b_lib\.|(?<![\w.]))" + helper + r"\("):
+                where = f"{path}: {helper}({args[0].strip() if args else ''}, ...)"
+                # the name is a literal, or a choice between literals (`"sn_x_f64" if f64 else "sn_x"`)
+                names = re.findall(r'"(sn_[a-z0-9_]+)"', args[0]) if args else []
+                assert names and not re.sub(r'"sn_[a-z0-9_]+"|\bif\b|\belse\b|[\w.=\s]', "", args[0]), \
+                    f"{where}: the entry point's name must be a literal"
+                assert not any(a.strip().startswith("*") for a in args), f"{where}: *args cannot be counted"
+                got = len([a for a in args[1:] if not re.match(r"\s*host\s*=", a)]) - extra
+                for name in names:
+                    assert name in through_call, f"{where}: {name} is not declared in include/sparenet_hip.h"
+                    assert got == through_call[name], f"{where}: {got} arguments, _lib.call takes {through_call[name]} for {name}"
+                    checked += 1
+    assert checked >= PARENT_CHECKED, checked
+
+
+def test_package_converts_arguments_in_lib_only():
+    """Outside _lib.py the package holds no pointer, size or stream conversion and no direct `.sn_*(` call: every
+    call into the library goes through _lib.call, which checks it against the header."""
+    raw = re.compile(r"\b(?:fptr|iptr|dptr|hptr|c_void_p|c_size_t|cfloat|stream_of)\(|\.sn_[a-z0-9_]+\(")
+    left = [f"{path}:{i}: {line.strip()}" for path, src in _package_sources() if not path.endswith("_lib.py")
+            for i, line in enumerate(src.splitlines(), 1) if raw.search(line)]
+    assert not left, left
 
 
 def _env_switches(root):

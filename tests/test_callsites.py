@@ -1,6 +1,6 @@
-"""Every ctypes call site of the host-side mirror, exercised on the CPU against a stub of the library that only
-CONVERTS the arguments with the argtypes parsed from include/sparenet_hip.h (sparenet_amd/_lib.py): an argument of
-the wrong kind or count at any call site (a numpy integer where a C int is declared, a missing workspace size, a
+"""Every call site of the host-side mirror, exercised on the CPU through sparenet_amd._lib.call against a stub of
+the library that only CONVERTS what `call` hands it with the argtypes parsed from include/sparenet_hip.h: an argument
+of the wrong kind or count at any call site (a numpy integer where a C int is declared, a missing workspace, a
 float passed positionally for a pointer) fails here, without a GPU, instead of corrupting memory on one.
 No result is looked at: the stub computes nothing."""
 import ctypes
@@ -41,17 +41,16 @@ def stub(monkeypatch):
     real = L.lib()
     st = _Stub(real)
     monkeypatch.setattr(L, "_lib", st)
-    want = {"fptr": torch.float32, "iptr": torch.int32, "dptr": torch.float64}
+    # what `call` has prepared per function, with the stub's converting function in place of the library's
+    monkeypatch.setattr(L, "_calls", {name: (getattr(st, name),) + spec[1:] for name, spec in L._calls.items()})
 
-    def fake_ptr(t, dtype, name):
+    def fake_address(t, dtype, name, host=False):      # _lib._address without the device check: CPU tensors stand in
         assert isinstance(t, torch.Tensor), name
-        assert t.dtype == dtype, f"{name}: expected {dtype}, got {t.dtype}"
+        assert dtype is None or t.dtype == dtype, f"{name}: expected {dtype}, got {t.dtype}"
         assert t.is_contiguous(), name
-        return ctypes.c_void_p(t.data_ptr() or 8)
+        return t.data_ptr() or 8
 
-    monkeypatch.setattr(L, "ptr", fake_ptr)
-    for k, dt in want.items():
-        monkeypatch.setattr(L, k, lambda t, name, _dt=dt: fake_ptr(t, _dt, name))
+    monkeypatch.setattr(L, "_address", fake_address)
     monkeypatch.setattr(L, "stream_of", lambda t: ctypes.c_void_p(0))
     return st
 
