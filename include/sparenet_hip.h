@@ -507,7 +507,8 @@ int sn_depth_project_backward(const float *data, long npoints, const float *matr
 /* The same for up to 8 views at once (the views of a ComputeDepthMaps sweep become part of the batch:
  * pixel / z / feat are [nviews, npoints], zminmax [nviews, 2], normalisation per view as in the reference;
  * g_data [npoints, 3] receives the sum over the views).  matrices16: nviews x 16 host floats.
- * workspace: 32 bytes per view. */
+ * workspace: 32 bytes per view.  The single-view pair above equals these calls with nviews = 1 (the same
+ * kernels, launched with grid caps of its own). */
 int sn_depth_project_forward_views(const float *data, long npoints, const float *matrices16, int nviews,
                                    float extent, float *pixel, float *z, unsigned *zminmax, float *feat,
                                    void *stream);

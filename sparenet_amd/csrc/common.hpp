@@ -150,6 +150,21 @@ inline bool knobs_per_call() {
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// workgroups of a grid-stride launch over `total` elements: one thread per element, at least 1, at most `cap`
+inline int grid_blocks(long total, int cap, int threads = 256) {
+  const long b = (total + threads - 1) / threads;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// order-preserving float -> unsigned (total order of the non-NaN floats; -0 sorts below +0), and back
+__device__ __forceinline__ unsigned ordered_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ordered_float(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
 // A workspace is described ONCE, by a layout function that takes its arrays from a Carver in order and returns the
 // struct of pointers.  On the caller's base pointer that carves the workspace; on a null base it only measures
 // (every pointer comes back null), which is what the sn_*_workspace_bytes exports and the "workspace too small" checks

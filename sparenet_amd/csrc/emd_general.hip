@@ -33,27 +33,20 @@ constexpr int kTile = 1024;             // targets per LDS tile (16 KiB)
 // lanes a bid launch aims for: 256 CUs x 4 SIMDs x 8 waves x 64.  Measured at B=32, 0.005 / 50 iterations (ms per
 // call, 16000 -> 16000 and 3000 -> 16384): 2^17 28.8 / 2.53, 2^18 21.7 / 2.27, 2^19 16.6 / 1.45, 2^20 16.3 / 1.51
 constexpr long kLanesWanted = 1L << 19;
+// cap of the per-element launches; every total is >= 1 (the entry points require b, n, m >= 1), so the floor of
+// sn::grid_blocks never acts
 constexpr int kMaxEltBlocks = 2048;
 
 struct GenWs {
   float *price;                 // [b, m]
   int *assign_inv;              // [b, m] bidder holding the target, -1
-  unsigned *max_key;            // [b, m] running maximum increment, as inc_key
+  unsigned *max_key;            // [b, m] running maximum increment, as sn::ordered_key
   unsigned long long *max_idx;  // [b, m] (stamp << 32) | j of the window's winner; stamp = iteration + 1
   int *bid;                     // [b, n] target of the bidder's last bid
   float *bid_inc;               // [b, n] its increment
   int *list[2];                 // [b, n] unassigned bidders of an iteration, any order
   int *cnt[2];                  // [b]    their number
 };
-
-// order-preserving float -> unsigned (total order of the non-NaN floats; -0 sorts below +0)
-__device__ __forceinline__ unsigned inc_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_inc(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // lanes per bidder: the power of two <= 64 that gives the launch about kLanesWanted lanes (every cloud is assumed to
 // have as many bidders as this one).  cnt * G < 2 * kLanesWanted / B whenever G > 1 (see bid_blocks).
@@ -89,11 +82,6 @@ GenWs gen_layout(sn::Carver &c, int b, int n, int m) {
   return w;
 }
 
-int elt_blocks(long total) {
-  const long bl = (total + kGThreads - 1) / kGThreads;
-  return (int)(bl < kMaxEltBlocks ? bl : kMaxEltBlocks);
-}
-
 // Ragged batches (sn_emd_forward_ragged / sn_emd_backward_ragged): the kernels below take the padded widths as n and m
 // -- the strides of every array -- and cloud i has its first lengths1[i] rows as bidders and its first lengths2[i] rows
 // as targets.  Dense calls pass no lengths and kRagged = false: every row counts.
@@ -120,7 +108,7 @@ __global__ __launch_bounds__(kGThreads) void gen_init_kernel(int B, int n, int m
   for (long e = first; e < (long)B * m; e += stride) {
     w.price[e] = 0.f;
     w.assign_inv[e] = -1;
-    w.max_key[e] = inc_key(0.f);  // max_increments starts at 0 (emd_module.py:49)
+    w.max_key[e] = sn::ordered_key(0.f);  // max_increments starts at 0 (emd_module.py:49)
     w.max_idx[e] = 0ull;          // ... and max_idx at 0: a stale index 0 from the start
   }
   for (long e = first; e < (long)B * n; e += stride) {
@@ -219,7 +207,7 @@ __global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
     a.w.bid[o] = t.best_i;
     a.w.bid_inc[o] = inc;
     if (t.best_i >= 0)  // -1 only for non-finite inputs: such a bidder never wins
-      atomicMax(&a.w.max_key[(size_t)i * m + t.best_i], inc_key(inc));
+      atomicMax(&a.w.max_key[(size_t)i * m + t.best_i], sn::ordered_key(inc));
   }
 }
 
@@ -232,7 +220,7 @@ __global__ __launch_bounds__(kGThreads) void emd_general_window_kernel(int n, in
     const int t = w.bid[(size_t)i * n + j];
     if (t < 0) continue;
     const size_t ot = (size_t)i * m + t;
-    if (in_window(w.bid_inc[(size_t)i * n + j], key_inc(w.max_key[ot])))
+    if (in_window(w.bid_inc[(size_t)i * n + j], sn::ordered_float(w.max_key[ot])))
       atomicMax(&w.max_idx[ot], ((unsigned long long)stamp << 32) | (unsigned)j);
   }
 }
@@ -262,7 +250,7 @@ __global__ __launch_bounds__(kGThreads) void emd_general_assign_kernel(int n, in
           }
           w.assign_inv[ot] = j;
           w.price[ot] += w.bid_inc[(size_t)i * n + j];
-          w.max_key[ot] = inc_key(-1e9f);
+          w.max_key[ot] = sn::ordered_key(-1e9f);
         }
       } else if (!last) {
         push = j;
@@ -489,7 +477,8 @@ int forward_launches(const char *what, const float *xyz1, const float *xyz2, int
   const GenWs w = gen_layout(carver, b, n, m);
   SN_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace too small (%zu < %zu)", what, workspace_bytes,
              carver.bytes());
-  gen_init_kernel<kRagged><<<elt_blocks((long)b * (m > n ? m : n)), kGThreads, 0, s>>>(b, n, m, assignment, w, r);
+  gen_init_kernel<kRagged><<<sn::grid_blocks((long)b * (m > n ? m : n), kMaxEltBlocks, kGThreads), kGThreads, 0, s>>>(
+      b, n, m, assignment, w, r);
   BidArgs ba;
   ba.B = b;
   ba.n = n;
@@ -511,8 +500,8 @@ int forward_launches(const char *what, const float *xyz1, const float *xyz2, int
     if (!last) emd_general_window_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, (unsigned)it + 1, w);
     emd_general_assign_kernel<<<list_grid, kGThreads, 0, s>>>(n, m, cur, last, w, assignment);
   }
-  emd_general_dist_kernel<kRagged><<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, assignment, dist,
-                                                                                r);
+  emd_general_dist_kernel<kRagged><<<sn::grid_blocks((long)b * n, kMaxEltBlocks, kGThreads), kGThreads, 0, s>>>(
+      b, n, m, xyz1, xyz2, assignment, dist, r);
   return sn::launch_status(what);
 }
 
@@ -529,12 +518,13 @@ int backward_launches(const char *what, const float *xyz1, const float *xyz2, co
                workspace_bytes, carver.bytes());
     SN_HIP(hipMemsetAsync(w.count, 0, (size_t)b * m * 4, s));
   }
-  emd_general_bwd1_kernel<kRagged><<<elt_blocks((long)b * n), kGThreads, 0, s>>>(b, n, m, xyz1, xyz2, graddist,
-                                                                                assignment, gradxyz1, w.count, r);
+  emd_general_bwd1_kernel<kRagged><<<sn::grid_blocks((long)b * n, kMaxEltBlocks, kGThreads), kGThreads, 0, s>>>(
+      b, n, m, xyz1, xyz2, graddist, assignment, gradxyz1, w.count, r);
   if (gradxyz2) {
     emd_general_bwd_scan_kernel<<<b, kSortThreads, 0, s>>>(m, w);
     emd_general_bwd_scatter_kernel<kRagged><<<b, kSortThreads, 0, s>>>(n, m, assignment, gradxyz1, w, r);
-    emd_general_bwd_sum_kernel<<<elt_blocks((long)b * m), kGThreads, 0, s>>>(b, n, m, w, gradxyz2);
+    emd_general_bwd_sum_kernel<<<sn::grid_blocks((long)b * m, kMaxEltBlocks, kGThreads), kGThreads, 0, s>>>(b, n, m, w,
+                                                                                                           gradxyz2);
   }
   return sn::launch_status(what);
 }

@@ -21,10 +21,7 @@ __device__ __forceinline__ void corners(float p, int &lo, int &up) {
   if (lo == up) up += 1;
 }
 
-int lin_blocks(long total, int threads = 256) {
-  const long b = (total + threads - 1) / threads;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr int kMaxLinBlocks = 8192;  // cap of the grid-stride launches
 
 __global__ __launch_bounds__(256) void gridding_fwd_kernel(int npts, int s, int nverts,
                                                            const float *__restrict__ ptcloud,
@@ -279,7 +276,7 @@ extern "C" int sn_gridding_forward(const float *ptcloud, int b, int npts, int sc
   SN_HIP(hipMemsetAsync(grid, 0, (size_t)b * nverts * 4, st));
   const long total = (long)b * npts;
   if (total > 0)
-    gridding_fwd_kernel<<<lin_blocks(total), 256, 0, st>>>(npts, s, nverts, ptcloud, grid, weights,
+    gridding_fwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, st>>>(npts, s, nverts, ptcloud, grid, weights,
                                                            indexes, total, 0);
   return sn::launch_status("sn_gridding_forward");
 }
@@ -295,7 +292,7 @@ extern "C" int sn_gridding_forward_padded(const float *ptcloud, int b, int npts,
   const long total = (long)b * npts;
   if (total > 0) {
     SN_REQUIRE(ptcloud && weights && indexes, "sn_gridding_forward_padded: null pointer");
-    gridding_fwd_kernel<<<lin_blocks(total), 256, 0, st>>>(npts, s, nverts, ptcloud, grid, weights,
+    gridding_fwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, st>>>(npts, s, nverts, ptcloud, grid, weights,
                                                            indexes, total, 1);
   }
   return sn::launch_status("sn_gridding_forward_padded");
@@ -315,9 +312,8 @@ extern "C" int sn_gridding_dist_forward(const float *ptcloud, int b, int npts, i
   const long total = (long)b * npts;
   if (total == 0) return 0;
   SN_REQUIRE(ptcloud && weights && indexes, "sn_gridding_dist_forward: null pointer");
-  gridding_dist_fwd_kernel<<<lin_blocks(total), 256, 0, st>>>(npts, min_x, min_y, min_z, (int)ly, (int)lz,
-                                                              nslots, ptcloud, grid, weights, indexes,
-                                                              total);
+  gridding_dist_fwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, st>>>(
+      npts, min_x, min_y, min_z, (int)ly, (int)lz, nslots, ptcloud, grid, weights, indexes, total);
   return sn::launch_status("sn_gridding_dist_forward");
 }
 
@@ -328,7 +324,7 @@ extern "C" int sn_gridding_backward(const float *grad_grid, const float *weights
   const long total = (long)b * npts;
   if (total == 0) return 0;
   SN_REQUIRE(grad_grid && weights && indexes && grad_ptcloud, "sn_gridding_backward: null pointer");
-  gridding_bwd_kernel<<<lin_blocks(total), 256, 0, sn::as_stream(stream)>>>(
+  gridding_bwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, sn::as_stream(stream)>>>(
       npts, nverts, grad_grid, weights, indexes, grad_ptcloud, total);
   return sn::launch_status("sn_gridding_backward");
 }
@@ -339,7 +335,7 @@ extern "C" int sn_gridding_reverse_forward(const float *grid, int b, int scale, 
   SN_REQUIRE(b >= 1 && scale >= 1 && scale <= 1024, "sn_gridding_reverse_forward: bad sizes");
   const int n3 = scale * scale * scale;
   const long total = (long)b * n3;
-  gridding_rev_fwd_kernel<<<lin_blocks(total), 256, 0, sn::as_stream(stream)>>>(scale, n3, grid,
+  gridding_rev_fwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, sn::as_stream(stream)>>>(scale, n3, grid,
                                                                                 ptcloud, total);
   return sn::launch_status("sn_gridding_reverse_forward");
 }
@@ -353,7 +349,7 @@ extern "C" int sn_gridding_reverse_backward(const float *grad_ptcloud, const flo
   const long total = (long)b * n3;
   hipStream_t st = sn::as_stream(stream);
   SN_HIP(hipMemsetAsync(grad_grid, 0, (size_t)total * 4, st));
-  gridding_rev_bwd_kernel<<<lin_blocks(total), 256, 0, st>>>(scale, n3, grad_ptcloud, grid, ptcloud,
+  gridding_rev_bwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, st>>>(scale, n3, grad_ptcloud, grid, ptcloud,
                                                              grad_grid, total);
   return sn::launch_status("sn_gridding_reverse_backward");
 }
@@ -367,9 +363,9 @@ extern "C" int sn_cubic_forward(const float *ptcloud, const float *feat, int b, 
   SN_REQUIRE(ptcloud && feat && out && idx, "sn_cubic_forward: null pointer");
   const int nv = 8 * ns * ns * ns, cub = scale * scale * scale;
   hipStream_t st = sn::as_stream(stream);
-  cubic_index_kernel<<<lin_blocks(pts), 256, 0, st>>>(npts, scale, ns, nv, ptcloud, idx, pts);
+  cubic_index_kernel<<<sn::grid_blocks(pts, kMaxLinBlocks), 256, 0, st>>>(npts, scale, ns, nv, ptcloud, idx, pts);
   const long total = pts * nv * c;
-  cubic_gather_kernel<<<lin_blocks(total), 256, 0, st>>>(npts, c, cub, nv, feat, idx, out, total);
+  cubic_gather_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, st>>>(npts, c, cub, nv, feat, idx, out, total);
   return sn::launch_status("sn_cubic_forward");
 }
 
@@ -384,7 +380,7 @@ extern "C" int sn_cubic_backward(const float *grad_out, const int *idx, int b, i
   const long total = (long)b * npts * nv * c;
   if (total == 0) return 0;
   SN_REQUIRE(grad_out && idx, "sn_cubic_backward: null pointer");
-  cubic_scatter_kernel<<<lin_blocks(total), 256, 0, st>>>(npts, c, cub, nv, grad_out, idx, grad_feat,
-                                                          total);
+  cubic_scatter_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, st>>>(npts, c, cub, nv, grad_out, idx,
+                                                                              grad_feat, total);
   return sn::launch_status("sn_cubic_backward");
 }

@@ -171,10 +171,7 @@ __global__ __launch_bounds__(256) void graph_feature_bwd_kernel(const float *__r
   }
 }
 
-int blocks_for(long total) {
-  const long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 65535 ? 65535 : b));
-}
+constexpr int kMaxBlocks = 65535;  // cap of the grid-stride launches
 
 }  // namespace
 
@@ -206,7 +203,8 @@ extern "C" int sn_graph_feature_forward(const float *x, const long long *idx, in
   SN_REQUIRE(x && idx && out, "sn_graph_feature_forward: null pointer");
   SN_REQUIRE(b >= 1 && c >= 1 && n >= 1 && k >= 1, "sn_graph_feature_forward: bad sizes");
   const long total = (long)b * c * n * k;
-  graph_feature_fwd_kernel<<<blocks_for(total), 256, 0, sn::as_stream(stream)>>>(x, idx, c, n, k, total, out);
+  graph_feature_fwd_kernel<<<sn::grid_blocks(total, kMaxBlocks), 256, 0, sn::as_stream(stream)>>>(
+      x, idx, c, n, k, total, out);
   return sn::launch_status("sn_graph_feature_forward");
 }
 
@@ -239,10 +237,11 @@ extern "C" int sn_graph_feature_backward(const float *grad_out, const long long 
   hipStream_t s = sn::as_stream(stream);
   const long edges = (long)b * n * k;
   SN_HIP(hipMemsetAsync(w.offs, 0, (size_t)b * n * 4, s));
-  graph_count_kernel<<<blocks_for(edges), 256, 0, s>>>(idx, n, k, edges, w.offs);
+  graph_count_kernel<<<sn::grid_blocks(edges, kMaxBlocks), 256, 0, s>>>(idx, n, k, edges, w.offs);
   graph_scan_kernel<<<b, 1024, 0, s>>>(w.offs, n);
-  graph_fill_kernel<<<blocks_for(edges), 256, 0, s>>>(idx, n, k, edges, w.offs, w.elist);
+  graph_fill_kernel<<<sn::grid_blocks(edges, kMaxBlocks), 256, 0, s>>>(idx, n, k, edges, w.offs, w.elist);
   const long total = (long)b * c * n;
-  graph_feature_bwd_kernel<<<blocks_for(total), 256, 0, s>>>(grad_out, w.offs, w.elist, c, n, k, total, grad_x);
+  graph_feature_bwd_kernel<<<sn::grid_blocks(total, kMaxBlocks), 256, 0, s>>>(grad_out, w.offs, w.elist, c, n, k,
+                                                                               total, grad_x);
   return sn::launch_status("sn_graph_feature_backward");
 }

@@ -1025,10 +1025,7 @@ __global__ __launch_bounds__(256) void gather_bwd_kernel(int c, int n, int m,
   }
 }
 
-static int lin_blocks(long total) {
-  const long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+constexpr int kMaxLinBlocks = 4096;  // cap of the grid-stride launches
 
 }  // namespace
 
@@ -1233,7 +1230,7 @@ extern "C" int sn_gather_forward(const float *feat, const int *idx, int b, int c
   SN_REQUIRE(feat && idx && out, "sn_gather_forward: null pointer");
   SN_REQUIRE(b >= 1 && c >= 1 && n >= 1 && m >= 1, "sn_gather_forward: bad sizes");
   const long total = (long)b * c * m;
-  gather_fwd_kernel<<<lin_blocks(total), 256, 0, sn::as_stream(stream)>>>(c, n, m, feat, idx, out,
+  gather_fwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, sn::as_stream(stream)>>>(c, n, m, feat, idx, out,
                                                                           total);
   return sn::launch_status("sn_gather_forward");
 }
@@ -1245,6 +1242,6 @@ extern "C" int sn_gather_backward(const float *grad_out, const int *idx, int b, 
   hipStream_t s = sn::as_stream(stream);
   SN_HIP(hipMemsetAsync(grad_feat, 0, (size_t)b * c * n * 4, s));
   const long total = (long)b * c * m;
-  gather_bwd_kernel<<<lin_blocks(total), 256, 0, s>>>(c, n, m, grad_out, idx, grad_feat, total);
+  gather_bwd_kernel<<<sn::grid_blocks(total, kMaxLinBlocks), 256, 0, s>>>(c, n, m, grad_out, idx, grad_feat, total);
   return sn::launch_status("sn_gather_backward");
 }

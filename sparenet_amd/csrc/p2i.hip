@@ -28,15 +28,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned ord_f32(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float unord_f32(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) {
   return v < lo ? lo : (v > hi ? hi : v);
 }
@@ -93,7 +84,7 @@ __global__ __launch_bounds__(256) void p2i_max_init_kernel(const float *__restri
                                                            long total) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (long)gridDim.x * blockDim.x)
-    img[e] = ((unsigned long long)ord_f32(background[e]) << 32) | 0xFFFFFFFFull;
+    img[e] = ((unsigned long long)sn::ordered_key(background[e]) << 32) | 0xFFFFFFFFull;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -153,7 +144,7 @@ __device__ __forceinline__ float max_sq_inside(float radius) {
 __device__ __forceinline__ void splat_exact(const SplatHit &hh, unsigned long long *img,
                                             float radius) {
   const float v = hh.f * cos_weight(__builtin_sqrtf(hh.r), radius);  // hh.r holds dx*dx+dy*dy
-  atomicMax(img + hh.pix, ((unsigned long long)ord_f32(v) << 32) | hh.low);
+  atomicMax(img + hh.pix, ((unsigned long long)sn::ordered_key(v) << 32) | hh.low);
 }
 
 template <int LPP>
@@ -219,7 +210,7 @@ __global__ __launch_bounds__(256) void p2i_max_splat_kernel(
         const float ra = __builtin_amdgcn_sqrtf(s2[i]);  // ~1 ulp: only feeds the bound
         const float wq = __builtin_amdgcn_cosf(ra * rev_scale) * 0.5f + 0.5f;
         const float ub = f >= 0.f ? f * (wq + 2e-5f) : f * __builtin_fmaxf(wq - 2e-5f, 0.f);
-        pass = !(ord_f32(ub) < cur[i]);  // can still reach (or tie with) the current value
+        pass = !(sn::ordered_key(ub) < cur[i]);  // can still reach (or tie with) the current value
       }
       const unsigned long long m = __ballot(pass);
       if (m) {
@@ -814,7 +805,7 @@ __global__ __launch_bounds__(256) void p2i_max_finalize_kernel(
        e += (long)gridDim.x * blockDim.x) {
     const unsigned long long k = img[e];
     const unsigned low = (unsigned)k;
-    out[e] = unord_f32((unsigned)(k >> 32));
+    out[e] = sn::ordered_float((unsigned)(k >> 32));
     ids[e] = low == 0xFFFFFFFFu ? -1 : (int)(0xFFFFFFFEu - low);
   }
 }
@@ -1025,10 +1016,7 @@ int check_common(const char *fn, int npoints, int channels, int batch, int h, in
   return 0;
 }
 
-int lin_blocks(long total) {
-  const long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+constexpr int kMaxLinBlocks = 4096;  // cap of the grid-stride launches
 
 // ---------------------------------------------------------------------------------------
 // max backward, pixel-centric with EXACT accumulation (all radii of a call in one pass).
@@ -1379,13 +1367,12 @@ int tile_forward(const char *fn, const float *points, const float *feat, const i
   }
   SN_HIP(hipMemsetAsync(t.counts, 0, (size_t)cells * 4, s));
   if (npoints > 0)
-    p2i_bin_count_kernel<<<lin_blocks(npoints), 256, 0, s>>>(points, batch_inds, t.counts, npoints, batch,
-                                                             h, w, cells_x, cells_y, need);
+    p2i_bin_count_kernel<<<sn::grid_blocks(npoints, kMaxLinBlocks), 256, 0, s>>>(
+        points, batch_inds, t.counts, npoints, batch, h, w, cells_x, cells_y, need);
   p2i_bin_scan_kernel<<<batch, 1024, 0, s>>>(t.counts, t.offs, cells_x * cells_y, need);
   if (npoints > 0)
-    p2i_bin_scatter_kernel<<<lin_blocks(npoints), 256, 0, s>>>(points, feat, batch_inds, t.offs, t.srec,
-                                                               t.fmax_bits, npoints, channels, batch, h, w, cells_x,
-                                                               cells_y, need);
+    p2i_bin_scatter_kernel<<<sn::grid_blocks(npoints, kMaxLinBlocks), 256, 0, s>>>(
+        points, feat, batch_inds, t.offs, t.srec, t.fmax_bits, npoints, channels, batch, h, w, cells_x, cells_y, need);
   const int blocks = (int)((tiles + 3) / 4);
   const long chw = (long)channels * h * w;
   const long obstride = image_major ? (long)nradii * chw : chw, orstride = image_major ? chw : (long)batch * chw;
@@ -1453,7 +1440,7 @@ extern "C" int sn_p2i_max_forward(const float *points, const float *feat, const 
     return tile_forward("sn_p2i_max_forward", points, feat, batch_inds, background, npoints,
                         channels, batch, h, w, &radius, 1, 0, out, out_ids, workspace, s);
   const long px = (long)batch * channels * h * w;
-  p2i_max_init_kernel<<<lin_blocks(px), 256, 0, s>>>(background, img, px);
+  p2i_max_init_kernel<<<sn::grid_blocks(px, kMaxLinBlocks), 256, 0, s>>>(background, img, px);
   const long groups = (long)npoints * channels;
   if (groups > 0) {
     const int lpp = lanes_per_point(radius);
@@ -1473,7 +1460,7 @@ extern "C" int sn_p2i_max_forward(const float *points, const float *feat, const 
     if (sn::prof_enabled()) sn::prof_end("p2i_max_splat", s);
 #undef SN_SPLAT
   }
-  p2i_max_finalize_kernel<<<lin_blocks(px), 256, 0, s>>>(img, out, out_ids, px);
+  p2i_max_finalize_kernel<<<sn::grid_blocks(px, kMaxLinBlocks), 256, 0, s>>>(img, out, out_ids, px);
   return sn::launch_status("sn_p2i_max_forward");
 }
 
@@ -1531,7 +1518,7 @@ extern "C" int sn_p2i_max_backward(const float *out_grad, const int *out_ids, co
   SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_p2i_max_backward: workspace too small");
   hipStream_t s = sn::as_stream(stream);
   const long px = (long)batch * channels * h * w;
-  p2i_max_bwd_pixels_kernel<<<lin_blocks(px), 256, 0, s>>>(out_grad, out_ids, points, feat,
+  p2i_max_bwd_pixels_kernel<<<sn::grid_blocks(px, kMaxLinBlocks), 256, 0, s>>>(out_grad, out_ids, points, feat,
                                                            background_grad, contrib, channels, h, w,
                                                            radius, px);
   if (npoints > 0) {
@@ -1595,7 +1582,7 @@ extern "C" int sn_p2i_max_backward_multi(const float *out_grad, const int *out_i
                                                        image_major ? (long)nradii * channels * h * w : (long)channels * h * w,
                                                        image_major ? (long)channels * h * w : px);
   if (npoints > 0)
-    p2i_max_bwd_finish_kernel<<<lin_blocks((long)npoints * (2 + channels)), 256, 0, s>>>(
+    p2i_max_bwd_finish_kernel<<<sn::grid_blocks((long)npoints * (2 + channels), kMaxLinBlocks), 256, 0, s>>>(
         a.acc_pts, a.acc_feat, a.absmax, a.cls, points_grad, feat_grad, (long)npoints * 2,
         (long)npoints * channels, rmin);
   return sn::launch_status("sn_p2i_max_backward_multi");

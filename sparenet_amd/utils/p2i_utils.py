@@ -101,44 +101,13 @@ def transform(matrix, points):
     return out[:, :3] / out[:, 3:4]
 
 
-class DepthProjectFunction(torch.autograd.Function):
-    """(data [B,N,3], P@V as 16 host floats, image_size) -> (pixel_ijs [B*N,2], point_features
-    [B*N,1]): ComputeDepthMaps.project() followed by p2i's NDC -> pixel rescale, as two HIP
-    kernels each way (sn_depth_project_forward / _backward) instead of ~25 torch ops and their
-    autograd nodes per view."""
-
-    @staticmethod
-    def forward(ctx, data, matrix16, image_size):
-        pts = data.contiguous().float().view(-1, 3)
-        n = pts.size(0)
-        dev = pts.device
-        pixel = torch.empty(n, 2, device=dev)
-        feat = torch.empty(n, 1, device=dev)
-        z = torch.empty(n, device=dev)
-        zminmax = torch.empty(2, dtype=torch.int32, device=dev)
-        mat = (ctypes.c_float * 16)(*matrix16)
-        extent = float(image_size - 1)
-        _lib.call("sn_depth_project_forward", pts, n, mat, extent, pixel, z, zminmax, feat)
-        ctx.save_for_backward(pts, z, zminmax)
-        ctx.mat, ctx.extent, ctx.shape = mat, extent, data.shape
-        return pixel, feat
-
-    @staticmethod
-    def backward(ctx, g_pixel, g_feat):
-        pts, z, zminmax = ctx.saved_tensors
-        n = pts.size(0)
-        g_data = torch.empty_like(pts)
-        ws = torch.empty(32, dtype=torch.uint8, device=pts.device)
-        gp = g_pixel.contiguous().float() if g_pixel is not None else None
-        gf = g_feat.contiguous().float() if g_feat is not None else None
-        _lib.call("sn_depth_project_backward", pts, n, ctx.mat, ctx.extent, z, zminmax, gp, gf, ws, g_data)
-        return g_data.view(ctx.shape), None, None
-
-
 class DepthProjectViewsFunction(torch.autograd.Function):
-    """DepthProjectFunction for several views at once: (data [B,N,3], [V][16] host matrices, image_size) ->
-    (pixel_ijs [V*B*N, 2], point_features [V*B*N, 1]), view-major.  The depth feature is normalised per view
-    over the whole input tensor, exactly as V separate calls would; the backward sums the views' gradients."""
+    """(data [B,N,3], [V][16] host matrices P@V, image_size) -> (pixel_ijs [V*B*N, 2], point_features [V*B*N, 1]),
+    view-major: ComputeDepthMaps.project() followed by p2i's NDC -> pixel rescale, as two HIP kernels each way
+    instead of ~25 torch ops and their autograd nodes per view.  The depth feature is normalised per view over the
+    whole input tensor, exactly as V separate calls would; the backward sums the views' gradients.  One matrix
+    goes to sn_depth_project_forward / _backward, several to the _views pair: the same kernels, the single-view
+    pair with grid caps of its own."""
 
     @staticmethod
     def forward(ctx, data, matrices, image_size):
@@ -151,7 +120,10 @@ class DepthProjectViewsFunction(torch.autograd.Function):
         zminmax = torch.empty(2 * v, dtype=torch.int32, device=dev)
         mat = (ctypes.c_float * (16 * v))(*[x for m in matrices for x in m])
         extent = float(image_size - 1)
-        _lib.call("sn_depth_project_forward_views", pts, n, mat, v, extent, pixel, z, zminmax, feat)
+        if v == 1:
+            _lib.call("sn_depth_project_forward", pts, n, mat, extent, pixel, z, zminmax, feat)
+        else:
+            _lib.call("sn_depth_project_forward_views", pts, n, mat, v, extent, pixel, z, zminmax, feat)
         ctx.save_for_backward(pts, z, zminmax)
         ctx.mat, ctx.nviews, ctx.extent, ctx.shape = mat, v, extent, data.shape
         return pixel, feat
@@ -159,14 +131,25 @@ class DepthProjectViewsFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_pixel, g_feat):
         pts, z, zminmax = ctx.saved_tensors
-        n = pts.size(0)
+        n, v = pts.size(0), ctx.nviews
         g_data = torch.empty_like(pts)
-        ws = torch.empty(32 * ctx.nviews, dtype=torch.uint8, device=pts.device)
+        ws = torch.empty(32 * v, dtype=torch.uint8, device=pts.device)
         gp = g_pixel.contiguous().float() if g_pixel is not None else None
         gf = g_feat.contiguous().float() if g_feat is not None else None
-        _lib.call("sn_depth_project_backward_views", pts, n, ctx.mat, ctx.nviews, ctx.extent, z, zminmax, gp, gf, ws,
-                  g_data)
+        if v == 1:
+            _lib.call("sn_depth_project_backward", pts, n, ctx.mat, ctx.extent, z, zminmax, gp, gf, ws, g_data)
+        else:
+            _lib.call("sn_depth_project_backward_views", pts, n, ctx.mat, v, ctx.extent, z, zminmax, gp, gf, ws,
+                      g_data)
         return g_data.view(ctx.shape), None, None
+
+
+class DepthProjectFunction:
+    """One view: apply(data, matrix16, image_size) is DepthProjectViewsFunction.apply(data, [matrix16], image_size)."""
+
+    @staticmethod
+    def apply(data, matrix16, image_size):
+        return DepthProjectViewsFunction.apply(data, [matrix16], image_size)
 
 
 class ComputeDepthMaps(torch.nn.Module):
@@ -219,13 +202,25 @@ class ComputeDepthMaps(torch.nn.Module):
         point_features = 1.0 - (z - zmin) / (zmax - zmin)
         return pos_ijs, point_features
 
+    def _splat(self, pixel_ijs, point_features, images, npoints, radii):
+        """Max-splat the points of `images` images (npoints each, image-major in pixel_ijs) on a zero background,
+        once per radius (1..4 of them): [images, len(radii), S, S]."""
+        s = self.image_size
+        batch_inds = self._batch_inds(images, npoints, pixel_ijs.device)
+        shape = (images, 1, s, s)
+        if len(radii) > 1 and max(radii) <= 16.0:   # the zero background as a shape: nothing to allocate or read
+            background = shape
+        else:
+            background = torch.zeros(shape, dtype=pixel_ijs.dtype, device=pixel_ijs.device)
+        if len(radii) == 1:
+            return P2IMaxFunction.apply(pixel_ijs, point_features, batch_inds, background, 0, radii[0])
+        stacked = P2IMaxMultiFunction.apply(pixel_ijs, point_features, batch_inds, background, 0, radii, True)
+        return stacked.view(images, len(radii), s, s)      # [images,R,1,S,S] as the kernel wrote it
+
     def forward(self, data, view_id=0, radius_list=[10.0]):
         if view_id >= self.num_views:
             return None
         batch, npoints = data.size(0), data.size(1)
-        background = torch.zeros(batch, 1, self.image_size, self.image_size, dtype=data.dtype,
-                                 device=data.device)
-        batch_inds = self._batch_inds(batch, npoints, data.device)
         # the reference calls p2i() once per radius (:230-251); the projection, the depth feature,
         # the NDC -> pixel rescale that p2i() performs (cuda/p2i_op/__init__.py:117-121), the zero
         # background and the points do not depend on the radius, so they are computed once (on
@@ -237,16 +232,8 @@ class ComputeDepthMaps(torch.nn.Module):
             pos_ijs, point_features = self.project(data, view_id)
             pixel_ijs = (pos_ijs + 1) / 2 * self._extent.to(device=data.device, dtype=data.dtype)
         radii = [float(r) for r in radius_list]
-        maps = []
-        for i in range(0, len(radii), 4):
-            chunk = radii[i:i + 4]
-            if len(chunk) == 1:
-                maps.append(P2IMaxFunction.apply(pixel_ijs, point_features, batch_inds, background,
-                                                 0, chunk[0]))
-            else:
-                stacked = P2IMaxMultiFunction.apply(pixel_ijs, point_features, batch_inds,
-                                                    background, 0, chunk, True)   # [B,r,1,S,S], written that way
-                maps.append(stacked.view(batch, len(chunk), self.image_size, self.image_size))
+        maps = [self._splat(pixel_ijs, point_features, batch, npoints, radii[i:i + 4])
+                for i in range(0, len(radii), 4)]
         return maps[0] if len(maps) == 1 else torch.cat(maps, dim=1)
 
     def forward_views(self, data, view_ids=None, radius_list=[10.0]):
@@ -261,17 +248,7 @@ class ComputeDepthMaps(torch.nn.Module):
         if not (data.is_cuda and data.dtype == torch.float32 and 1 <= len(radii) <= 4 and 1 <= len(view_ids) <= 8):
             return torch.stack([self.forward(data, v, radius_list) for v in view_ids])
         batch, npoints, nv = data.size(0), data.size(1), len(view_ids)
-        s = self.image_size
         pixel_ijs, point_features = DepthProjectViewsFunction.apply(
-            data, [self._host_mats[v] for v in view_ids], s)
-        batch_inds = self._batch_inds(nv * batch, npoints, data.device)
-        if len(radii) > 1 and max(radii) <= 16.0:   # the zero background as a shape: nothing to allocate or read
-            stacked = P2IMaxMultiFunction.apply(pixel_ijs, point_features, batch_inds, (nv * batch, 1, s, s), 0,
-                                                radii, True)
-            return stacked.view(nv, batch, len(radii), s, s)      # [V*B,R,1,S,S] as the kernel wrote it
-        background = torch.zeros(nv * batch, 1, s, s, dtype=data.dtype, device=data.device)
-        if len(radii) == 1:
-            maps = P2IMaxFunction.apply(pixel_ijs, point_features, batch_inds, background, 0, radii[0])
-            return maps.view(nv, batch, 1, s, s)
-        stacked = P2IMaxMultiFunction.apply(pixel_ijs, point_features, batch_inds, background, 0, radii, True)
-        return stacked.view(nv, batch, len(radii), s, s)      # [V*B,R,1,S,S] as the kernel wrote it
+            data, [self._host_mats[v] for v in view_ids], self.image_size)
+        maps = self._splat(pixel_ijs, point_features, nv * batch, npoints, radii)
+        return maps.view(nv, batch, len(radii), self.image_size, self.image_size)

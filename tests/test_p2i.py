@@ -310,6 +310,68 @@ def test_hip_fused_projection_matches_torch_glue(projection, dev):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(1, 37), (2, 700), (3, 500)])   # under a wave; two 1024-thread blocks; tied extremes
+@pytest.mark.parametrize("projection", ["orthorgonal", "perspective"])
+def test_hip_one_view_is_the_views_path_with_one_view(projection, shape, dev):
+    """sn_depth_project_forward / _backward run the _views kernels with one view and grid caps of their own:
+    DepthProjectFunction equals DepthProjectViewsFunction with that one matrix and slice v of a call over all
+    eight views bit for bit, and so do the gradients of an upstream gradient on the pixel output alone (no
+    reduction, no atomics; the views kernel adds the views' terms in order).  With a gradient on the depth feature
+    the zmin / zmax sums meet through float64 atomics in no fixed order: the routes agree within 1e-5 of the
+    largest gradient, the bound test_hip_fused_projection_matches_torch_glue holds against float64."""
+    from sparenet_amd.utils.p2i_utils import ComputeDepthMaps, DepthProjectFunction, DepthProjectViewsFunction
+
+    B, N = shape
+    S, views, n = 64, (0, 3, 6), B * N
+    g = torch.Generator().manual_seed(23)
+    cdm = ComputeDepthMaps(projection, 1.0, S).to(dev)
+    mats = cdm._host_mats
+    base = torch.rand(B, N, 3, generator=g) - 0.5
+    if B == 3:
+        base[1, 7] = base[0, 3]          # duplicated points: ties at whatever extreme they reach
+        base[2, 9] = base[0, 3]
+    gp = (torch.rand(len(views), n, 2, generator=g) - 0.5).to(dev)
+    gf = (torch.rand(len(views), n, 1, generator=g) - 0.5).to(dev)
+
+    def run(fn, m):
+        d = base.clone().to(dev).requires_grad_(True)
+        return (d,) + fn(d, m, S)
+
+    def pixel_only(pix, g_pixel):
+        # autograd would hand the node a zero g_feat; applied directly, g_feat is absent
+        return pix.grad_fn.apply(g_pixel.reshape(-1, 2).contiguous(), None)[0]
+
+    def both(d, pix, feat, g_pixel, g_feat):
+        torch.autograd.backward([pix, feat], [g_pixel.reshape(-1, 2), g_feat.reshape(-1, 1)])
+        return d.grad
+
+    _, pix8, feat8 = run(DepthProjectViewsFunction.apply, mats)
+    pix8, feat8 = pix8.detach().view(8, n, 2).cpu().numpy(), feat8.detach().view(8, n, 1).cpu().numpy()
+    sum_pixel = sum_both = None
+    for k, v in enumerate(views):
+        d1, pix1, feat1 = run(DepthProjectFunction.apply, mats[v])
+        dv, pixv, featv = run(DepthProjectViewsFunction.apply, [mats[v]])
+        for name, one, many, ref in (("pixel", pix1, pixv, pix8[v]), ("feat", feat1, featv, feat8[v])):
+            assert np.array_equal(one.detach().cpu().numpy(), many.detach().cpu().numpy()), (name, v)
+            assert np.array_equal(one.detach().cpu().numpy(), ref), (name, v, "slice of all eight views")
+        g1, gv = pixel_only(pix1, gp[k]), pixel_only(pixv, gp[k])
+        assert np.array_equal(g1.cpu().numpy(), gv.cpu().numpy()), (v, "backward, pixel gradient only")
+        sum_pixel = g1 if sum_pixel is None else sum_pixel + g1
+        b1, bv = both(d1, pix1, feat1, gp[k], gf[k]), both(dv, pixv, featv, gp[k], gf[k])
+        err = float((b1 - bv).abs().max()) / float(bv.abs().max())
+        print(f"{projection} {shape} view {v}: one view vs views([v]), pixel + feat gradient: {err:.3g}")
+        assert err <= 1e-5, (v, err)
+        sum_both = b1 if sum_both is None else sum_both + b1
+    d3, pix3, feat3 = run(DepthProjectViewsFunction.apply, [mats[v] for v in views])
+    g3 = pixel_only(pix3, gp)
+    assert np.array_equal(sum_pixel.cpu().numpy(), g3.view(B, N, 3).cpu().numpy()), "sum of one-view gradients, pixel only"
+    b3 = both(d3, pix3, feat3, gp, gf)
+    err = float((sum_both - b3).abs().max()) / float(b3.abs().max())
+    print(f"{projection} {shape}: sum of one-view gradients vs views({list(views)}), pixel + feat gradient: {err:.3g}")
+    assert err <= 1e-5, err
+
+
+@pytest.mark.gpu
 def test_hip_depthmaps_vs_reference_golden(golden_dir, dev):
     """End to end ComputeDepthMaps on the GPU against maps rendered by the imported
     reference (CPU torch glue + reference functor semantics)."""
