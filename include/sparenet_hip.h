@@ -522,7 +522,10 @@ int sn_depth_project_backward_views(const float *data, long npoints, const float
  *          94-95; gridding.cu:29-211, 213-335).  ptcloud[b,npts,3] already
  *          scaled; bounds are [-scale/2, scale/2-1] per axis as
  *          cuda/gridding/__init__.py:16-19 passes them.
- * grid[b,scale^3] fully overwritten; weights[b,npts,8,3]; indexes[b,npts,8]. */
+ * grid[b,scale^3] fully overwritten; weights[b,npts,8,3]; indexes[b,npts,8].
+ * scale must be even and 2 <= scale <= 1024 (scale^3 vertices stay inside an int); both
+ * entry points refuse any other scale.  indexes holds the raw vertex index of every corner; a
+ * corner whose index is outside [0, scale^3) contributes nothing, forward and backward. */
 int sn_gridding_forward(const float *ptcloud, int b, int npts, int scale,
                         float *grid, float *weights, int *indexes,
                         void *stream);

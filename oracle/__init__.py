@@ -318,10 +318,12 @@ def cubic_backward(grad_out, idx, c, scale, ns):
 def knn(x, k):
     """x [B,C,N] -> idx [B,N,k]: the reference's ranking  |x_j|^2 - 2 x_i.x_j  (the CPU branch of
     models/sparenet_generator.py:872-875 up to the row constant) in float64, ascending, equal scores by
-    lower index."""
+    lower index; the point itself first (also among exact duplicates of it, as both HIP kernels force it)."""
     x = np.asarray(x, np.float64)
     inner = np.matmul(x.transpose(0, 2, 1), x)    # (a BLAS product: einsum's own loop takes 40 s at C = 512, N = 3000)
     score = (x * x).sum(1)[:, None, :] - 2.0 * inner
+    i = np.arange(x.shape[2])
+    score[:, i, i] = -np.inf
     return np.argsort(score, axis=2, kind="stable")[:, :, :k]
 
 

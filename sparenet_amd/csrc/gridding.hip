@@ -22,6 +22,9 @@ __device__ __forceinline__ void corners(float p, int &lo, int &up) {
 }
 
 constexpr int kMaxLinBlocks = 8192;  // cap of the grid-stride launches
+// both gridding entry points take the same scales: even (the grid spans [-scale/2, scale/2 - 1]), and at most
+// this, so that scale^3 vertices stay inside the kernels' int indexes
+constexpr int kMaxGridScale = 1024;
 
 __global__ __launch_bounds__(256) void gridding_fwd_kernel(int npts, int s, int nverts,
                                                            const float *__restrict__ ptcloud,
@@ -269,7 +272,8 @@ __global__ __launch_bounds__(256) void cubic_scatter_kernel(int npts, int c, int
 extern "C" int sn_gridding_forward(const float *ptcloud, int b, int npts, int scale, float *grid,
                                    float *weights, int *indexes, void *stream) {
   SN_REQUIRE(grid, "sn_gridding_forward: null pointer");
-  SN_REQUIRE(b >= 1 && npts >= 0 && scale >= 2, "sn_gridding_forward: bad sizes");
+  SN_REQUIRE(b >= 1 && npts >= 0 && scale >= 2 && scale % 2 == 0 && scale <= kMaxGridScale,
+             "sn_gridding_forward: bad sizes (need b >= 1, npts >= 0, an even scale in [2, %d])", kMaxGridScale);
   SN_REQUIRE(npts == 0 || (ptcloud && weights && indexes), "sn_gridding_forward: null pointer");
   const int s = scale / 2, nverts = 8 * s * s * s;
   hipStream_t st = sn::as_stream(stream);
@@ -284,8 +288,8 @@ extern "C" int sn_gridding_forward(const float *ptcloud, int b, int npts, int sc
 extern "C" int sn_gridding_forward_padded(const float *ptcloud, int b, int npts, int scale,
                                           float *grid, float *weights, int *indexes, void *stream) {
   SN_REQUIRE(grid, "sn_gridding_forward_padded: null pointer");
-  SN_REQUIRE(b >= 1 && npts >= 0 && scale >= 2 && scale % 2 == 0 && scale <= 1024,
-             "sn_gridding_forward_padded: bad sizes");
+  SN_REQUIRE(b >= 1 && npts >= 0 && scale >= 2 && scale % 2 == 0 && scale <= kMaxGridScale,
+             "sn_gridding_forward_padded: bad sizes (need b >= 1, npts >= 0, an even scale in [2, %d])", kMaxGridScale);
   const int s = scale / 2, nverts = 8 * s * s * s;
   hipStream_t st = sn::as_stream(stream);
   SN_HIP(hipMemsetAsync(grid, 0, (size_t)b * nverts * 4, st));

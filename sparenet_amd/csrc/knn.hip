@@ -10,7 +10,7 @@
 //   * sn_knn_topk: one wave per row ranks  s_j = |x_j|^2 - 2 x_i.x_j  (the row constant |x_i|^2
 //     does not change the order), every lane keeps the k smallest of its strided share in
 //     registers, then k wave-minimum extractions merge them; equal scores resolve to the lower
-//     index.  HBM bound: the matrix is read once (1.15 GB at B=32, N=3000).
+//     index, and the point itself is forced to the front (as in knn_mfma.hip).  HBM bound: the matrix is read once (1.15 GB at B=32, N=3000).
 //   * sn_graph_feature_forward / backward: out[b, c, n, j] = x[b, c, idx[b,n,j]] - x[b, c, n],
 //     out[b, C + c, n, j] = x[b, c, n]  (the cat((feature - x, x)).permute(0,3,1,2) of :899-905).
 #include "common.hpp"
@@ -27,6 +27,7 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(const float *__restrict__
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const long b = row / n;
+  const int self = (int)(row - b * n);
   const float *in = inner + row * n;
   const float *x2 = xx + b * n;
   // the lane's K smallest (score, index), ascending; (3e38, 2^31-1) = empty
@@ -38,7 +39,9 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(const float *__restrict__
     id[i] = 0x7fffffff;
   }
   for (int j = lane; j < n; j += 64) {
-    const float s = __builtin_fmaf(-2.f, in[j], x2[j]);
+    // the point itself first, also among duplicates of it (their scores are equal) and where rounding ranks a
+    // very close neighbour below it
+    const float s = j == self ? -3.0e38f : __builtin_fmaf(-2.f, in[j], x2[j]);
     if (s < v[K - 1]) {  // strided ascending j: an equal score never displaces an earlier index
       float cv = s;
       int ci = j;
