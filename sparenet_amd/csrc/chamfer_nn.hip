@@ -11,9 +11,8 @@
 //     current best distance R2max, and skips every superblock whose box is farther than that.
 //     The test runs for 64 superblocks at a time, lane = superblock.
 //   * pair level, on the matrix cores: u = |t|^2 - 2 t.q for 16 targets x 16 queries is one
-//     v_mfma_f32_16x16x4_f32 (exact fp32); a pair can only matter if u <= best_q - |q|^2 + slack.
-//     The slack 2^-18 (max|t|^2 + |q|^2) covers the fmaf chain's rounding, the stored |t|^2 and
-//     |q|^2 and the evaluation of the threshold; (1 + 2^-20) covers the rounding of the exact d.
+//     v_mfma_f32_16x16x4_f32 (exact fp32); a pair can only matter if u <= best_q - |q|^2 + slack
+//     (formats and margins: pair_filter.hpp).
 //   * survivors go to a per-wave LDS queue and are evaluated 64 at a time with the reference's
 //     expression; the result meets the query through a 64-bit LDS atomicMin on
 //     (bits of d) << 32 | k.  d >= 0, so its bit pattern orders like the value: the minimum key
@@ -23,10 +22,11 @@
 // it still has to search is already ~1.5 nearest-neighbour distances wide.
 #include "cloud_sort.hpp"
 #include "common.hpp"
+#include "pair_filter.hpp"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
+using namespace sn::pf;  // f4, the operand stream and box rows, the margins, min16 / hits4 / queue_append
 
 struct NnSide {       // one cloud in Morton order
   const float *xyz;   // [B, n, 3] as given
@@ -35,16 +35,9 @@ struct NnSide {       // one cloud in Morton order
   int *hist;          // [B, 4096] cell END offsets after the scatter
   float *bbox;        // [B, 6]
   f4 *sorted4;        // [B, nsb*64] {x, y, z, index bits}; padding: index -1
-  f4 *mstream;        // [B, nsb, 64] MFMA A operand, see emd.hip
-  float *sbbox;       // [B, nsb, 8] lo xyz, hi xyz, 0, 0
+  f4 *mstream;        // [B, nsb, 64] MFMA A operand (pair_filter.hpp)
+  float *sbbox;       // [B, nsb, 8] box rows (pair_filter.hpp)
 };
-
-__device__ __forceinline__ float exact_d(float tx, float ty, float tz, float qx, float qy, float qz) {
-#pragma clang fp contract(off)
-  const float dx = tx - qx, dy = ty - qy, dz = tz - qz;
-  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-  return (xx + yy) + zz;
-}
 
 // one wave per superblock: sorted coordinates, MFMA operand stream, bounding box
 __global__ __launch_bounds__(256) void nn_prepare_kernel(int B, NnSide S) {
@@ -59,43 +52,12 @@ __global__ __launch_bounds__(256) void nn_prepare_kernel(int B, NnSide S) {
     const float *t = S.xyz + (b * S.n + (valid ? k : 0)) * 3;
     const float x = valid ? t[0] : 0.f, y = valid ? t[1] : 0.f, z = valid ? t[2] : 0.f;
     S.sorted4[sb * 64 + lane] = f4{x, y, z, __int_as_float(k)};
-    // padding never passes the filter: |t|^2 = 3e38
-    const float tt = valid ? (x * x + y * y) + z * z : 3.0e38f;
-    float *m = reinterpret_cast<float *>(S.mstream + sb * 64);
-    const int q = (lane >> 4) & 3, c = lane & 15;
-    m[(0 * 16 + c) * 4 + q] = -2.f * x;
-    m[(1 * 16 + c) * 4 + q] = -2.f * y;
-    m[(2 * 16 + c) * 4 + q] = -2.f * z;
-    m[(3 * 16 + c) * 4 + q] = tt;
-    float lo[3] = {valid ? x : 3e38f, valid ? y : 3e38f, valid ? z : 3e38f};
-    float hi[3] = {valid ? x : -3e38f, valid ? y : -3e38f, valid ? z : -3e38f};
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-      for (int s = 1; s < 64; s <<= 1) {
-        lo[a] = __builtin_fminf(lo[a], __shfl_xor(lo[a], s));
-        hi[a] = __builtin_fmaxf(hi[a], __shfl_xor(hi[a], s));
-      }
-    if (lane < 8) {
-      const float v = lane == 0 ? lo[0] : lane == 1 ? lo[1] : lane == 2 ? lo[2] : lane == 3 ? hi[0]
-                    : lane == 4 ? hi[1] : lane == 5 ? hi[2] : 0.f;
-      S.sbbox[sb * 8 + lane] = v;
-    }
+    store_operand(S.mstream + sb * 64, lane, x, y, z, valid ? norm2(x, y, z) : kFar);  // padding never passes
+    float lo[3] = {valid ? x : kFar, valid ? y : kFar, valid ? z : kFar};
+    float hi[3] = {valid ? x : -kFar, valid ? y : -kFar, valid ? z : -kFar};
+    sn::wave_minmax3(lo, hi);
+    store_box_row(S.sbbox, sb, lane, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
   }
-}
-
-__device__ __forceinline__ float min16(const f4 a, const f4 b, const f4 c, const f4 d) {
-  const float m0 = __builtin_fminf(__builtin_fminf(a.x, a.y), a.z);
-  const float m1 = __builtin_fminf(__builtin_fminf(a.w, b.x), b.y);
-  const float m2 = __builtin_fminf(__builtin_fminf(b.z, b.w), c.x);
-  const float m3 = __builtin_fminf(__builtin_fminf(c.y, c.z), c.w);
-  const float m4 = __builtin_fminf(__builtin_fminf(d.x, d.y), d.z);
-  const float m5 = __builtin_fminf(__builtin_fminf(m0, m1), d.w);
-  return __builtin_fminf(__builtin_fminf(m2, m3), __builtin_fminf(m4, m5));
-}
-
-__device__ __forceinline__ unsigned hits4(const f4 d, float thr, int shift) {
-  return ((d.x <= thr ? 1u : 0u) | (d.y <= thr ? 2u : 0u) | (d.z <= thr ? 4u : 0u) |
-          (d.w <= thr ? 8u : 0u)) << shift;
 }
 
 constexpr int kQueue = 128;
@@ -105,15 +67,6 @@ struct NnTab {  // per-wave LDS
   unsigned long long key[64];  // (bits of the best d) << 32 | its lowest k
   unsigned queue[kQueue];      // sorted target position | query lane << 26
 };
-
-// squared distance between two boxes, rounded down a little
-__device__ __forceinline__ float box_gap2(const float *qlo, const float *qhi, float lx, float ly,
-                                          float lz, float hx, float hy, float hz) {
-  const float gx = __builtin_fmaxf(__builtin_fmaxf(lx - qhi[0], qlo[0] - hx), 0.f);
-  const float gy = __builtin_fmaxf(__builtin_fmaxf(ly - qhi[1], qlo[1] - hy), 0.f);
-  const float gz = __builtin_fmaxf(__builtin_fmaxf(lz - qhi[2], qlo[2] - hz), 0.f);
-  return ((gx * gx + gy * gy) + gz * gz) * 0.9999f;
-}
 
 __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide S2,
                                                         float *__restrict__ dist1,
@@ -142,23 +95,13 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
   const bool active = qk >= 0;
   unsigned long long key = ~0ull;
   if (active) {
-    const float *box = T.bbox + b * 6;
-    unsigned cq[3];
-    const float v[3] = {q.x, q.y, q.z};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float ext = box[3 + a] - box[a];
-      cq[a] = sort_coord(v[a], box[a], sort_scale(ext));
-    }
-    const int c = (int)morton3_4bit(cq[0], cq[1], cq[2]);
-    const int start = c > 0 ? T.hist[b * kSortCells + c - 1] : 0;  // END of the previous cell
-    int lo = start - 2;
+    int lo = sort_cell_start(T.hist + b * kSortCells, q.x, q.y, q.z, T.bbox + b * 6) - 2;
     lo = lo < 0 ? 0 : (lo > T.n - 8 ? T.n - 8 : lo);
     lo = lo < 0 ? 0 : lo;
     const int cnt = T.n < 8 ? T.n : 8;
     for (int p = lo; p < lo + cnt; ++p) {
       const f4 t = t4[p];
-      const float d = exact_d(t.x, t.y, t.z, q.x, q.y, q.z);
+      const float d = sq_dist(t.x, t.y, t.z, q.x, q.y, q.z);
       const unsigned long long kk = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(t.w);
       key = kk < key ? kk : key;
     }
@@ -167,21 +110,10 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
   W.y[lane] = q.y;
   W.z[lane] = q.z;
   W.key[lane] = key;
-  float qlo[3] = {active ? q.x : 3e38f, active ? q.y : 3e38f, active ? q.z : 3e38f};
-  float qhi[3] = {active ? q.x : -3e38f, active ? q.y : -3e38f, active ? q.z : -3e38f};
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-    for (int s = 1; s < 64; s <<= 1) {
-      qlo[a] = __builtin_fminf(qlo[a], __shfl_xor(qlo[a], s));
-      qhi[a] = __builtin_fmaxf(qhi[a], __shfl_xor(qhi[a], s));
-    }
-  float tmax = 0.f;  // upper bound of every stored |t|^2: the far corner of the targets' box
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float l0 = T.bbox[b * 6 + a], h0 = T.bbox[b * 6 + 3 + a];
-    tmax += __builtin_fmaxf(l0 * l0, h0 * h0);
-  }
-  tmax *= 1.0001f;
+  float qlo[3] = {active ? q.x : kFar, active ? q.y : kFar, active ? q.z : kFar};
+  float qhi[3] = {active ? q.x : -kFar, active ? q.y : -kFar, active ? q.z : -kFar};
+  sn::wave_minmax3(qlo, qhi);
+  const float tmax = far_corner2(T.bbox + b * 6);
 
   // the four queries this lane filters for (column col of query group g), MFMA B operand
   float thr[4], base[4], bop[4];
@@ -191,8 +123,8 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
 #pragma clang fp contract(off)
     const int c = 16 * g + col;
     const float x = W.x[c], y = W.y[c], z = W.z[c];
-    const float xx = (x * x + y * y) + z * z;
-    base[g] = 3.814697265625e-06f * (tmax + xx) - xx;
+    const float xx = norm2(x, y, z);
+    base[g] = kSlack18 * (tmax + xx) - xx;
     live[g] = W.key[c] != ~0ull;
     bop[g] = row == 0 ? x : (row == 1 ? y : (row == 2 ? z : 1.0f));
   }
@@ -205,7 +137,7 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float best = __uint_as_float((unsigned)(W.key[16 * g + col] >> 32));
-      thr[g] = live[g] ? __builtin_fmaf(best, 1.00000095367431640625f, base[g]) : -3.0e38f;
+      thr[g] = live[g] ? __builtin_fmaf(best, kUp20, base[g]) : -kFar;
     }
   };
   refresh();
@@ -217,7 +149,7 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
       const unsigned e = W.queue[first + lane];
       const int c = (int)(e >> 26);
       const f4 t = t4[e & 0x3ffffffu];
-      const float d = exact_d(t.x, t.y, t.z, W.x[c], W.y[c], W.z[c]);
+      const float d = sq_dist(t.x, t.y, t.z, W.x[c], W.y[c], W.z[c]);
       atomicMin(&W.key[c], ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(t.w));
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -232,7 +164,7 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
     if (sbl < T.nsb) {
       const f4 lo4 = *reinterpret_cast<const f4 *>(sbb + (size_t)sbl * 8);
       const f4 hi4 = *reinterpret_cast<const f4 *>(sbb + (size_t)sbl * 8 + 4);
-      visit = box_gap2(qlo, qhi, lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y) <= r2max;
+      visit = box_gap2(lo4, hi4, qlo, qhi) <= r2max;
     }
     unsigned long long todo = __ballot(visit);
     while (todo) {
@@ -248,21 +180,12 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
         const f4 d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bop[g], zero, 0, 0, 0);
         const f4 d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bop[g], zero, 0, 0, 0);
         if (__builtin_expect(__any(min16(d0, d1, d2, d3) <= thr[g]), 0)) {
-          // bit 4 q + r  <->  sorted target position 64 sb + 16 q + 4 row + r
           unsigned hm = hits4(d0, thr[g], 0) | hits4(d1, thr[g], 4) | hits4(d2, thr[g], 8) |
                         hits4(d3, thr[g], 12);
           while (__any(hm != 0)) {
-            const bool has = hm != 0;
-            const int i = has ? __builtin_ctz(hm) : 0;
-            hm &= hm - 1;
-            const unsigned long long bal = __ballot(has);
-            const int pos = qcount + (int)__builtin_amdgcn_mbcnt_hi(
-                                         (unsigned)(bal >> 32),
-                                         __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-            if (has)
-              W.queue[pos] = (unsigned)(sb * 64 + 16 * (i >> 2) + 4 * row + (i & 3)) |
-                             ((unsigned)(16 * g + col) << 26);
-            qcount += __popcll(bal);
+            qcount = queue_append(W.queue, qcount, hm, [=](int i) {
+              return (unsigned)hit_position(sb * 64, i, row) | ((unsigned)(16 * g + col) << 26);
+            });
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             while (qcount >= 64) {
               qcount -= 64;
@@ -279,7 +202,7 @@ __global__ __launch_bounds__(256) void nn_search_kernel(int B, NnSide S1, NnSide
           if (sbl < T.nsb && ((todo >> lane) & 1ull)) {
             const f4 lo4 = *reinterpret_cast<const f4 *>(sbb + (size_t)sbl * 8);
             const f4 hi4 = *reinterpret_cast<const f4 *>(sbb + (size_t)sbl * 8 + 4);
-            still = box_gap2(qlo, qhi, lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y) <= r2max;
+            still = box_gap2(lo4, hi4, qlo, qhi) <= r2max;
           }
           todo = __ballot(still);
         }

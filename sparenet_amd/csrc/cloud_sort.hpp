@@ -7,6 +7,7 @@
 // point (23 us next to the count kernel's 24 at 32 x 16384 points; together now 30).
 #pragma once
 #include "common.hpp"
+#include "wave_dpp.hpp"
 
 namespace {
 
@@ -16,8 +17,8 @@ constexpr int kSortBits = 4;                     // grid side 2^bits per axis
 constexpr int kSortSide = 1 << kSortBits;
 constexpr int kSortCells = kSortSide * kSortSide * kSortSide;
 
-// grid coordinate of v inside [lo, lo + ext]: the ONE expression every kernel uses, so a point lands in the
-// same cell wherever its cell is recomputed
+// grid coordinate of v inside [lo, lo + ext]; with sort_cell below the ONE expression every kernel uses, so a point
+// lands in the same cell wherever its cell is recomputed
 __device__ __forceinline__ float sort_scale(float ext) { return ext > 0.f ? ((float)kSortSide - 0.001f) / ext : 0.f; }
 __device__ __forceinline__ unsigned sort_coord(float v, float lo, float scale) {
   const float f = (v - lo) * scale;
@@ -61,6 +62,20 @@ __device__ __forceinline__ unsigned morton3_4bit(unsigned x, unsigned y, unsigne
   return r;
 }
 
+// the cell of point (x, y, z) in a cloud whose bounding box is box = {lo xyz, hi xyz}, and where the cell's points
+// start in the sorted order (hist = the cloud's cell END offsets)
+__device__ __forceinline__ int sort_cell(float x, float y, float z, const float *box) {
+  const float v[3] = {x, y, z};
+  unsigned q[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) q[a] = sort_coord(v[a], box[a], sort_scale(box[3 + a] - box[a]));
+  return (int)morton3_4bit(q[0], q[1], q[2]);
+}
+__device__ __forceinline__ int sort_cell_start(const int *hist, float x, float y, float z, const float *box) {
+  const int c = sort_cell(x, y, z, box);
+  return c > 0 ? hist[c - 1] : 0;
+}
+
 // per cloud: bounding box -> cell histogram -> Hilbert-order permutation (one workgroup per cloud)
 struct SortSide {
   int n;
@@ -83,12 +98,7 @@ __device__ __forceinline__ void cloud_sort_body(int n, const float *__restrict__
       lo[a] = __builtin_fminf(lo[a], v);
       hi[a] = __builtin_fmaxf(hi[a], v);
     }
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-    for (int m = 1; m < 64; m <<= 1) {
-      lo[a] = __builtin_fminf(lo[a], __shfl_xor(lo[a], m));
-      hi[a] = __builtin_fmaxf(hi[a], __shfl_xor(hi[a], m));
-    }
+  sn::wave_minmax3(lo, hi);
   if ((tid & 63) == 0)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -97,7 +107,7 @@ __device__ __forceinline__ void cloud_sort_body(int n, const float *__restrict__
     }
   for (int c = tid; c < kSortCells; c += 1024) lh[c] = 0;
   __syncthreads();
-  float blo[3], scale[3];
+  float box[6];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     float l = red[a][0], h = red[3 + a][0];
@@ -105,18 +115,15 @@ __device__ __forceinline__ void cloud_sort_body(int n, const float *__restrict__
       l = __builtin_fminf(l, red[a][w]);
       h = __builtin_fmaxf(h, red[3 + a][w]);
     }
-    blo[a] = l;
-    scale[a] = sort_scale(h - l);
+    box[a] = l;
+    box[3 + a] = h;
     if (tid == 0) {
       bbox[b * 6 + a] = l;
       bbox[b * 6 + 3 + a] = h;
     }
   }
   for (int k = tid; k < n; k += 1024) {
-    unsigned q[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) q[a] = sort_coord(p[k * 3 + a], blo[a], scale[a]);
-    const int c = (int)morton3_4bit(q[0], q[1], q[2]);
+    const int c = sort_cell(p[k * 3], p[k * 3 + 1], p[k * 3 + 2], box);
     cell_of[(size_t)b * n + k] = c;
     atomicAdd(&lh[c], 1);
   }

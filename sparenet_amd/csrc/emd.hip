@@ -65,6 +65,7 @@ constexpr int kRecAny = 512, kRecWords = 544;
 
 
 using namespace sn::emd;  // Top2, bid_value, sq_dist, tie_key, top2_*, filter_* (emd_bid.hpp)
+using namespace sn::pf;   // f4, the operand stream and box rows, the margins, min16 / hits4 / queue_append (pair_filter.hpp)
 
 // order-preserving float max through integer atomics
 // (Round 6 measured WORKGROUP-scope atomics for teams that sit on one XCD -- the running maxima, the list heads, the bin
@@ -148,15 +149,8 @@ __device__ __forceinline__ int2 ldc2(const int *p) {  // 8-byte aligned pair
 //    read, both addressed by the stream position of a hit (one round trip).  Written by emd_init_kernel,
 //    the price refreshed by the Assign phase for the targets whose price changed (rank2[k] = p); the same
 //    price goes to prt, the transposed copy the coarse filter reads.
-//  * mstream: the MFMA A-operand of the coarse filter, price independent (written once).
-//    u_kj = |t_k|^2 - 2 t_k . x_j is a [targets x 4] . [4 x bidders] product with rows
-//    (-2x, -2y, -2z, |t|^2) and columns (x, y, z, 1).  v_mfma_f32_16x16x4_f32 takes ONE float
-//    per lane for A: lane l supplies A[i = l & 15][k = l >> 4].  A superblock of 64 targets is
-//    4 such operands; lane l's four values sit in one float4:
-//      mstream[(superblock * 64 + l)].q = component (l >> 4) of target 64 sb + 16 q + (l & 15)
-//    so a wave fetches 64 targets with one coalesced global_load_dwordx4 per lane.
-//  * sbbox: the bounding box of every block of 16 targets, for the pruning test.
-typedef float f4 __attribute__((ext_vector_type(4)));
+//  * mstream: the MFMA A-operand stream of the coarse filter (pair_filter.hpp), price independent (written once).
+//  * sbbox: the box row of every block of 16 targets, for the pruning test.
 
 struct EmdWs {
   int *assignment_inv;
@@ -224,34 +218,9 @@ __global__ void emd_init_kernel(int B, int n, const float *__restrict__ xyz2,
       ws.t4s[e] = f4{x, y, z, __int_as_float(k)};
       ws.pk[e] = make_float2(0.f, __int_as_float(k));
       ws.rank2[bb * n + k] = p;
-      const float tt = (x * x + y * y) + z * z;
-      float *m = reinterpret_cast<float *>(ws.mstream + (bb * (n >> 6) + (p >> 6)) * 64);
-      const int q = (p >> 4) & 3, c = p & 15;
-      m[(0 * 16 + c) * 4 + q] = -2.f * x;
-      m[(1 * 16 + c) * 4 + q] = -2.f * y;
-      m[(2 * 16 + c) * 4 + q] = -2.f * z;
-      m[(3 * 16 + c) * 4 + q] = tt;
+      store_operand(ws.mstream + (bb * (n >> 6) + (p >> 6)) * 64, p, x, y, z, norm2(x, y, z));
     }
   }
-}
-
-// min / max over each row of 16 lanes, left in every lane of the row (four DPP steps)
-__device__ __forceinline__ float row16_min(float v) {
-  v = __builtin_fminf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true)));
-  v = __builtin_fminf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true)));
-  v = __builtin_fminf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, true)));
-  v = __builtin_fminf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, true)));
-  return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = __builtin_fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true)));
-  v = __builtin_fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true)));
-  v = __builtin_fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, true)));
-  v = __builtin_fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, true)));
-  return v;
-}
-__device__ __forceinline__ float lane_value(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
 // bounding box of every block of 16 consecutive targets of the Morton-ordered stream (the rows of one
@@ -266,13 +235,10 @@ __global__ __launch_bounds__(256) void emd_sbbox_kernel(int B, int n, const floa
     float lo[3], hi[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      lo[a] = row16_min(t[a]);
-      hi[a] = row16_max(t[a]);
+      lo[a] = sn::row16_min(t[a]);
+      hi[a] = sn::row16_max(t[a]);
     }
-    const int c = lane & 15;
-    if (c < 8)
-      ws.sbbox[(sb * 4 + (lane >> 4)) * 8 + c] = c == 0 ? lo[0] : c == 1 ? lo[1] : c == 2 ? lo[2]
-                                               : c == 3 ? hi[0] : c == 4 ? hi[1] : c == 5 ? hi[2] : 0.f;
+    store_box_row(ws.sbbox, sb * 4 + (lane >> 4), lane & 15, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
   }
 }
 
@@ -303,25 +269,14 @@ __global__ __launch_bounds__(kThreads) void emd_seed_kernel(int B, int n,
     const long bb = e / n;
     const long je = bb * n + ws.perm1[e];
     const float x = xyz1[je * 3 + 0], y = xyz1[je * 3 + 1], z = xyz1[je * 3 + 2];
-    const float *box = ws.bbox + bb * 6;
-    unsigned q[3];
-    const float v[3] = {x, y, z};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float ext = box[3 + a] - box[a];
-      q[a] = sort_coord(v[a], box[a], sort_scale(ext));
-    }
-    const int c = (int)morton3_4bit(q[0], q[1], q[2]);
-    const int start = c > 0 ? ws.hist[bb * kSortCells + c - 1] : 0;  // END of the previous cell
-    int lo = start - 4;
+    int lo = sort_cell_start(ws.hist + bb * kSortCells, x, y, z, ws.bbox + bb * 6) - 4;
     lo = lo < 0 ? 0 : (lo > n - 16 ? n - 16 : lo);
     float s1 = 3e38f, s2 = 3e38f;
     int k1 = -1, k2 = -1;
     for (int p = lo; p < lo + 16; ++p) {  // the prepared stream: one 16-byte record per position, no second gather
       const f4 t = ws.t4s[bb * n + p];
       const int k = __float_as_int(t.w);
-      const float dx = t.x - x, dy = t.y - y, dz = t.z - z;
-      const float sq = (dx * dx + dy * dy) + dz * dz;
+      const float sq = sq_dist(t.x, t.y, t.z, x, y, z);
       if (sq < s1) {
         s2 = s1;
         k2 = k1;
@@ -439,9 +394,7 @@ __device__ __forceinline__ void emit_bid(const BidOut &A, size_t o, int j, int r
 //   per-target A'_k of the precise filter is replaced by its upper bound over all targets
 //   (prices never fall below `price_floor`), which makes the threshold a per-LANE constant.
 //   Cost: 16 MFMA (32 cycles each, exact fp32 = an fmaf chain) + ~44 VALU per 4096 pairs.
-//   The slack 2^-18 (max|t|^2 + |x|^2) covers the fmaf chain's rounding (4 roundings of
-//   partial sums <= 2 (|t|^2 + |x|^2)), the rounding of the stored |t|^2 and of |x|^2, and
-//   the fp32 evaluation of T' itself.
+//   The slack and the other margins: pair_filter.hpp.
 // hit queue.  Level-1 hits are rare and scattered over the lanes, so they are not evaluated
 //   in place: (target, bidder) pairs are appended to a per-wave LDS queue and handled 64 at a
 //   time with every lane busy.
@@ -461,21 +414,6 @@ __device__ __forceinline__ void emit_bid(const BidOut &A, size_t o, int j, int r
 // Work split: S = 2^k <= 16 waves of ONE workgroup share a group of 64 bidders, wave s taking
 // the superblocks sb with sb mod S == s; their partial top-2's meet in LDS in arrival order.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float min16(const f4 a, const f4 b, const f4 c, const f4 d) {
-  const float m0 = __builtin_fminf(__builtin_fminf(a.x, a.y), a.z);
-  const float m1 = __builtin_fminf(__builtin_fminf(a.w, b.x), b.y);
-  const float m2 = __builtin_fminf(__builtin_fminf(b.z, b.w), c.x);
-  const float m3 = __builtin_fminf(__builtin_fminf(c.y, c.z), c.w);
-  const float m4 = __builtin_fminf(__builtin_fminf(d.x, d.y), d.z);
-  const float m5 = __builtin_fminf(__builtin_fminf(m0, m1), d.w);
-  return __builtin_fminf(__builtin_fminf(m2, m3), __builtin_fminf(m4, m5));
-}
-
-__device__ __forceinline__ unsigned hits4(const f4 d, float thr, int shift) {
-  return ((d.x <= thr ? 1u : 0u) | (d.y <= thr ? 2u : 0u) | (d.z <= thr ? 4u : 0u) |
-          (d.w <= thr ? 8u : 0u)) << shift;
-}
-
 constexpr int kQueue = 128;  // a round appends <= 64 pairs to < 64 left-overs
 
 struct WaveTab {  // per-wave LDS: the 64 bidders it serves, and its hit queue
@@ -501,7 +439,7 @@ struct GroupAcc {  // per bidder group of a workgroup: the arrival-order merge o
 // level-1 threshold T' of one bidder: base = slack - |x|^2 is fixed, cm grows
 __device__ __forceinline__ float coarse_threshold(float cm, float base, float a_max) {
   const float r = a_max - filter_thr(cm);
-  return __builtin_fmaf(r * __builtin_fabsf(r), 1.00000095367431640625f, base);
+  return __builtin_fmaf(r * __builtin_fabsf(r), kUp20, base);
 }
 
 // =======================================================================================
@@ -730,16 +668,15 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
       const float x1 = ga.sx[lane], y1 = ga.sy[lane], z1 = ga.sz[lane];
       {
 #pragma clang fp contract(off)
-        const float xx = (x1 * x1 + y1 * y1) + z1 * z1;
-        own_slack2 = 2.f * 3.814697265625e-06f * (tmax + xx);
+        own_slack2 = 2.f * kSlack18 * (tmax + norm2(x1, y1, z1));
         const float v[3] = {x1, y1, z1};
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-          const float lo = row16_min(active ? v[a] : 3.0e38f), hi = row16_max(active ? v[a] : -3.0e38f);
+          const float lo = sn::row16_min(active ? v[a] : kFar), hi = sn::row16_max(active ? v[a] : -kFar);
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            blo[g][a] = lane_value(lo, 16 * g);
-            bhi[g][a] = lane_value(hi, 16 * g);
+            blo[g][a] = sn::lane_value(lo, 16 * g);
+            bhi[g][a] = sn::lane_value(hi, 16 * g);
           }
         }
       }
@@ -773,8 +710,8 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
 #pragma clang fp contract(off)
         const int cc = 16 * g + col;
         const float x = T.x[cc], y = T.y[cc], z = T.z[cc];
-        const float xx = (x * x + y * y) + z * z;
-        const float base = 7.62939453125e-06f * (tmax + xx) - xx;  // 2^-17: see above (2^-18 would do without prices)
+        const float xx = norm2(x, y, z);
+        const float base = kSlack17 * (tmax + xx) - xx;  // 2^-17: see above (2^-18 would do without prices)
         const float cmv = T.cm[cc];
         if (!up) {
           thr[g] = coarse_threshold(cmv, base, a_max);
@@ -783,7 +720,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
           const float ct = filter_thr(cmv);
           const bool open = a_max - ct >= 0.f;  // false for idle lanes (cm = 3e38) as well
           const float gam = ct - 3.0f;
-          thr[g] = open ? __builtin_fmaf(gam * gam, 1.0000152587890625f, base) : -3.0e38f;
+          thr[g] = open ? __builtin_fmaf(gam * gam, kUp16, base) : -kFar;
           bop2[g] = row == 0 ? 1.0f : (row == 1 && open ? gam : 0.f);
         }
       }
@@ -831,11 +768,11 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
 
     float r2g[4];
     auto refresh_reach = [&]() {
-      const float v = row16_max(active ? coarse_threshold(T.cm[lane], own_slack2, a_max) : -3.0e38f);
+      const float v = sn::row16_max(active ? coarse_threshold(T.cm[lane], own_slack2, a_max) : -kFar);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const float r = lane_value(v, 16 * g);
-        r2g[g] = r > 0.f ? r * 1.0001f : r;
+        const float r = sn::lane_value(v, 16 * g);
+        r2g[g] = r > 0.f ? r * kUp : r;
       }
     };
     refresh_reach();
@@ -846,12 +783,7 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
     auto worth = [&](const f4 lo4, const f4 hi4) {
       unsigned m = 0;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float gx = __builtin_fmaxf(__builtin_fmaxf(lo4.x - bhi[g][0], blo[g][0] - lo4.w), 0.f);
-        const float gy = __builtin_fmaxf(__builtin_fmaxf(lo4.y - bhi[g][1], blo[g][1] - hi4.x), 0.f);
-        const float gz = __builtin_fmaxf(__builtin_fmaxf(lo4.z - bhi[g][2], blo[g][2] - hi4.y), 0.f);
-        m |= (((gx * gx + gy * gy) + gz * gz) * 0.9999f <= r2g[g] ? 1u : 0u) << g;
-      }
+      for (int g = 0; g < 4; ++g) m |= (box_gap2(lo4, hi4, blo[g], bhi[g]) <= r2g[g] ? 1u : 0u) << g;
       return m;
     };
     auto quad_mask = [&](unsigned m) {
@@ -935,20 +867,11 @@ __device__ __forceinline__ void bid_group(const BidCtx &c, WaveTab &T, GroupAcc 
             STAMP(2)
             while (__any(hm != 0)) {
               COUNT(10, 1)
-              const bool has = hm != 0;
-              const int i = has ? __builtin_ctz(hm) : 0;
-              hm &= hm - 1;
-              const unsigned long long bal = __ballot(has);
-              const int pos = qcount + (int)__builtin_amdgcn_mbcnt_hi(
-                                           (unsigned)(bal >> 32),
-                                           __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-              if (has)
-                T.queue[pos] = (unsigned)(kb + 16 * (i >> 2) + 4 * row + (i & 3)) |
-                               ((unsigned)(16 * g + col) << 20);
-              qcount += __popcll(bal);
-#ifdef SN_BID_STAMPS
-              st[11] += __popcll(bal);
-#endif
+              COUNT(11, -qcount)
+              qcount = queue_append(T.queue, qcount, hm, [=](int i) {
+                return (unsigned)hit_position(kb, i, row) | ((unsigned)(16 * g + col) << 20);
+              });
+              COUNT(11, qcount)
               while (qcount >= 64) {
                 qcount -= 64;
                 STAMP(14)
@@ -1061,10 +984,8 @@ struct ScanLds {
 };
 
 __device__ __forceinline__ bool box_within(const f4 A, const f4 B, float x, float y, float z, float r2) {
-  const float gx = __builtin_fmaxf(__builtin_fmaxf(A.x - x, x - A.w), 0.f);
-  const float gy = __builtin_fmaxf(__builtin_fmaxf(A.y - y, y - B.x), 0.f);
-  const float gz = __builtin_fmaxf(__builtin_fmaxf(A.z - z, z - B.y), 0.f);
-  return ((gx * gx + gy * gy) + gz * gz) * 0.9999f <= r2;
+  const float p[3] = {x, y, z};
+  return box_gap2(A, B, p, p) <= r2;
 }
 // The same with the box's OWN price bound (round 6).  B.z = A'max of the box: an upper bound of filter_target(price) over
 // its targets -- from the price floor (the same for every box) or, on contested / off-surface clouds, from the smallest
@@ -1074,8 +995,8 @@ __device__ __forceinline__ bool box_within(const f4 A, const f4 B, float x, floa
 // blocks it cannot want: 20-35 % fewer blocks late in a contested call (tools/sim/auction_regime_stats.c).
 __device__ __forceinline__ bool box_within_priced(const f4 A, const f4 B, float x, float y, float z, float cthr, float base) {
   const float r = B.z - cthr;
-  const float v = __builtin_fmaf(r * __builtin_fabsf(r), 1.00000095367431640625f, base);
-  return box_within(A, B, x, y, z, v > 0.f ? v * 1.0001f : v);
+  const float v = __builtin_fmaf(r * __builtin_fabsf(r), kUp20, base);
+  return box_within(A, B, x, y, z, v > 0.f ? v * kUp : v);
 }
 
 #define SN_DPP_F(v, ctrl) __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), ctrl, 0xf, 0xf, true))
@@ -1136,8 +1057,7 @@ __device__ __forceinline__ void bid_scan(const BidCtx &c, ScanLds &SL, const int
       }
       {
 #pragma clang fp contract(off)
-        const float xx = (x1 * x1 + y1 * y1) + z1 * z1;
-        base = 2.f * 3.814697265625e-06f * (c.tmax + xx);
+        base = 2.f * kSlack18 * (c.tmax + norm2(x1, y1, z1));
         cthr = filter_thr(cm);
       }
     }
@@ -1486,18 +1406,11 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   for (int b = team; b < a.B; b += a.tg.teams) {
     if (a.rmask && a.rmask[b] == 0u) continue;  // recovery pass: a cloud the team launch finished
     const size_t o = (size_t)b * n;
-    float tmax = 0.f;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      const float lo = a.ws.bbox[b * 6 + ax], hi = a.ws.bbox[b * 6 + 3 + ax];
-      tmax += __builtin_fmaxf(lo * lo, hi * hi);
-    }
-    tmax *= 1.0001f;
     BidCtx c;
     c.n = n;
     c.nsb = nsb;
     c.eps = a.eps;
-    c.tmax = tmax;
+    c.tmax = far_corner2(a.ws.bbox + b * 6);
     c.o = o;
     c.p1 = a.xyz1 + o * 3;
     c.p2 = a.xyz2 + o * 3;

@@ -4,8 +4,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pair_filter.hpp"
+
 namespace sn {
 namespace emd {
+
+using pf::sq_dist;  // s of bid_value, on its own
 
 struct Top2 {
   float best, better;
@@ -19,14 +23,6 @@ __device__ __forceinline__ float bid_value(float tx, float ty, float tz, float p
   const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
   const float s = (xx + yy) + zz;
   return (float)((3.0 - (double)__builtin_sqrtf(s)) - (double)p);
-}
-
-__device__ __forceinline__ float sq_dist(float tx, float ty, float tz, float x1, float y1,
-                                         float z1) {
-#pragma clang fp contract(off)
-  const float dx = tx - x1, dy = ty - y1, dz = tz - z1;
-  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-  return (xx + yy) + zz;
 }
 
 // Exact ties at the top.  The reference's Bid resolves d_k == best to

@@ -58,10 +58,6 @@ extern "C" int sn_mds_debug_stamps(unsigned long long *out8, int reset) {
 
 namespace {
 
-__device__ __forceinline__ float lane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m, int width) {
   const unsigned lo = __shfl_xor((unsigned)v, m, width);
   const unsigned hi = __shfl_xor((unsigned)(v >> 32), m, width);
@@ -886,7 +882,7 @@ __global__ __launch_bounds__(1024) void mds_dense_team_kernel(
           eq = __ballot(cv == mv && cl == ml);
         }
         const int wq = (int)__builtin_ctzll(eq);
-        const float qx = lane_f(cx, wq), qy = lane_f(cy, wq), qz = lane_f(cz, wq);
+        const float qx = sn::lane_value(cx, wq), qy = sn::lane_value(cy, wq), qz = sn::lane_value(cz, wq);
         const unsigned ql = (unsigned)__builtin_amdgcn_readlane((int)cl, wq);
         if (lane == 0) s_picks[q] = make_float4(qx, qy, qz, __uint_as_float(ql));
         np = q + 1;

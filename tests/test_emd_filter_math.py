@@ -5,8 +5,8 @@ within the bidder's REACH, r2 = coarse_threshold(cm, slack, a_max) x 1.0001, and
 s <= r |r|, r = filter_target(price) - filter_thr(cm), where cm is the smaller value of two previous favourites (any
 two distinct targets) at today's prices.  The claim that makes this exact: every target whose value reaches cm
 survives both tests -- so the top two values of the survivors are the top two of the full scan.  The formulas
-below restate sparenet_amd/csrc/emd.hip (filter_target, filter_thr, filter_pass, coarse_threshold, box_within,
-bid_value) operation by operation in numpy float32; the clouds include large offsets (heavy cancellation in
+below restate sparenet_amd/csrc (emd_bid.hpp: filter_target, filter_thr, filter_pass, bid_value; pair_filter.hpp: sq_dist,
+box_gap2 and the margins; emd.hip: coarse_threshold, box_within) operation by operation in numpy float32; the clouds include large offsets (heavy cancellation in
 |t|^2 - 2 t.x), lattices (exact ties), tight clusters and prices of very different sizes."""
 import zlib
 
