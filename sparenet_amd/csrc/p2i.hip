@@ -79,12 +79,17 @@ __device__ __forceinline__ float radius_of(float dx, float dy) {
   return __builtin_sqrtf(dx * dx + dy * dy);
 }
 
+// The packed atomicMax orders keys, and the key of -0 sorts below that of +0, where the reference's `out < v` sees two
+// equal values (a rim pixel's f * 0 is -0 for a negative feature): every zero enters the key as +0, so that zeros
+// tie -- the background keeps the pixel, the lowest point id wins among points -- as in the sequential walk.
+__device__ __forceinline__ float one_zero(float v) { return v == 0.f ? 0.f : v; }
+
 __global__ __launch_bounds__(256) void p2i_max_init_kernel(const float *__restrict__ background,
                                                            unsigned long long *__restrict__ img,
                                                            long total) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (long)gridDim.x * blockDim.x)
-    img[e] = ((unsigned long long)sn::ordered_key(background[e]) << 32) | 0xFFFFFFFFull;
+    img[e] = ((unsigned long long)sn::ordered_key(one_zero(background[e])) << 32) | 0xFFFFFFFFull;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -143,7 +148,7 @@ __device__ __forceinline__ float max_sq_inside(float radius) {
 
 __device__ __forceinline__ void splat_exact(const SplatHit &hh, unsigned long long *img,
                                             float radius) {
-  const float v = hh.f * cos_weight(__builtin_sqrtf(hh.r), radius);  // hh.r holds dx*dx+dy*dy
+  const float v = one_zero(hh.f * cos_weight(__builtin_sqrtf(hh.r), radius));  // hh.r holds dx*dx+dy*dy
   atomicMax(img + hh.pix, ((unsigned long long)sn::ordered_key(v) << 32) | hh.low);
 }
 
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(256) void p2i_max_splat_kernel(
         const float ra = __builtin_amdgcn_sqrtf(s2[i]);  // ~1 ulp: only feeds the bound
         const float wq = __builtin_amdgcn_cosf(ra * rev_scale) * 0.5f + 0.5f;
         const float ub = f >= 0.f ? f * (wq + 2e-5f) : f * __builtin_fmaxf(wq - 2e-5f, 0.f);
-        pass = !(sn::ordered_key(ub) < cur[i]);  // can still reach (or tie with) the current value
+        pass = !(sn::ordered_key(one_zero(ub)) < cur[i]);  // can still reach (or tie with) the current value
       }
       const unsigned long long m = __ballot(pass);
       if (m) {
@@ -799,13 +804,14 @@ __global__ __launch_bounds__(256, 6) void p2i_gather_max_kernel(
 }
 
 __global__ __launch_bounds__(256) void p2i_max_finalize_kernel(
-    const unsigned long long *__restrict__ img, float *__restrict__ out, int *__restrict__ ids,
-    long total) {
+    const unsigned long long *__restrict__ img, const float *__restrict__ background, float *__restrict__ out,
+    int *__restrict__ ids, long total) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (long)gridDim.x * blockDim.x) {
     const unsigned long long k = img[e];
     const unsigned low = (unsigned)k;
-    out[e] = sn::ordered_float((unsigned)(k >> 32));
+    // a pixel no point won is the background itself (its key carries a -0 as +0)
+    out[e] = low == 0xFFFFFFFFu ? background[e] : sn::ordered_float((unsigned)(k >> 32));
     ids[e] = low == 0xFFFFFFFFu ? -1 : (int)(0xFFFFFFFEu - low);
   }
 }
@@ -1460,7 +1466,7 @@ extern "C" int sn_p2i_max_forward(const float *points, const float *feat, const 
     if (sn::prof_enabled()) sn::prof_end("p2i_max_splat", s);
 #undef SN_SPLAT
   }
-  p2i_max_finalize_kernel<<<sn::grid_blocks(px, kMaxLinBlocks), 256, 0, s>>>(img, out, out_ids, px);
+  p2i_max_finalize_kernel<<<sn::grid_blocks(px, kMaxLinBlocks), 256, 0, s>>>(img, background, out, out_ids, px);
   return sn::launch_status("sn_p2i_max_forward");
 }
 

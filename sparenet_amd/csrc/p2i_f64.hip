@@ -29,6 +29,10 @@ __device__ __forceinline__ double unord_f64(unsigned long long k) {
   return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
+// the key of -0 sorts below that of +0, where the reference's `out < v` sees two equal values (a rim pixel's f * 0 is
+// -0 for a negative feature): every zero enters the key as +0, so that zeros tie as in the sequential walk
+__device__ __forceinline__ double one_zero(double v) { return v == 0.0 ? 0.0 : v; }
+
 template <typename F>
 __device__ __forceinline__ void for_each_pixel(double py, double px, int h, int w, double radius, F f) {
   if (!(fabs(py) < 1e15) || !(fabs(px) < 1e15)) return;  // NaN / inf: int conversion undefined
@@ -47,7 +51,7 @@ __device__ __forceinline__ double cos_weight64(double r, double radius) { return
 __global__ __launch_bounds__(256) void f64_init_kernel(const double *__restrict__ bg, long total,
                                                       unsigned long long *__restrict__ key, int *__restrict__ ids) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    key[e] = ord_f64(bg[e]);
+    key[e] = ord_f64(one_zero(bg[e]));
     ids[e] = 0x7fffffff;
   }
 }
@@ -68,7 +72,7 @@ __global__ __launch_bounds__(256) void f64_max_fwd_kernel(const double *__restri
     for_each_pixel(points[pid * 2], points[pid * 2 + 1], h, w, radius, [&](int y, int x, double, double, double r) {
       const size_t index = (((size_t)b * channels + c) * h + y) * w + x;
       const double v = f * cos_weight64(r, radius);
-      const unsigned long long k = ord_f64(v);
+      const unsigned long long k = ord_f64(one_zero(v));
       if (PASS == 0) {
         atomicMax(&key[index], k);
       } else if (k == key[index] && bg[index] < v) {  // attains the maximum, and the maximum beat the background
@@ -78,11 +82,15 @@ __global__ __launch_bounds__(256) void f64_max_fwd_kernel(const double *__restri
   }
 }
 
-__global__ __launch_bounds__(256) void f64_max_finish_kernel(const unsigned long long *__restrict__ key, long total,
+__global__ __launch_bounds__(256) void f64_max_finish_kernel(const unsigned long long *__restrict__ key,
+                                                            const double *__restrict__ bg, long total,
                                                             double *__restrict__ out, int *__restrict__ ids) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     out[e] = unord_f64(key[e]);
-    if (ids[e] == 0x7fffffff) ids[e] = -1;
+    if (ids[e] == 0x7fffffff) {  // no point won: the background itself (its key carries a -0 as +0)
+      ids[e] = -1;
+      out[e] = bg[e];
+    }
   }
 }
 
@@ -201,7 +209,7 @@ extern "C" int sn_p2i_max_forward_f64(const double *points, const double *feat, 
     f64_max_fwd_kernel<1><<<blocks_of(groups), 256, 0, s>>>(points, feat, batch_inds, background, npoints,
                                                             channels, batch, h, w, radius, key, out_ids);
   }
-  f64_max_finish_kernel<<<blocks_of(total), 256, 0, s>>>(key, total, out, out_ids);
+  f64_max_finish_kernel<<<blocks_of(total), 256, 0, s>>>(key, background, total, out, out_ids);
   return sn::launch_status("sn_p2i_max_forward_f64");
 }
 

@@ -10,6 +10,7 @@ autograd path and compared with a reference built from the forward's own indices
 - finite entries lie within the op's stated bound of the float64 reference (bit-equal for the ops that are
   bit-equal to the oracle).
 """
+import functools
 import math
 
 import numpy as np
@@ -251,6 +252,54 @@ def test_p2i_max_backward_zero_upstream_and_large_finite(dev):
             og.reshape(-1)[won[1]] = 3.2e38
         out.backward(_t(og, dev))
         _p2i_max_check(og, ids, pk, fk, radii, p.grad.cpu().numpy(), f.grad.cpu().numpy(), ("large", kind))
+
+
+@functools.lru_cache(None)
+def _crowded_oracle(S, C, R):
+    import p2i_cases as pc
+
+    case = pc.crowded(S, C)
+    out, ids = oracle.p2i_max_forward(case.pts, case.feat, case.bi, case.bg, R)
+    out.setflags(write=False)
+    ids.setflags(write=False)
+    return out, ids
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regime", ["wide", "signed"])
+@pytest.mark.parametrize("image_major", [False, True], ids=["radius-major", "image-major"])
+@pytest.mark.parametrize("radii", [[0.7, 1.0], [1.0, 2.0]], ids=["R0.7-1", "R1-2"])
+@pytest.mark.parametrize("S,C", [(64, 1), (64, 3), (40, 1), (40, 3), (43, 3)])
+def test_p2i_max_backward_crowded_regions(S, C, radii, image_major, regime, dev):
+    """One point per pixel (tests/p2i_cases.crowded): a full 32 x 32 region holds about 1020 distinct winners, twice the
+    512 slots of the hash table of p2i_max_bwd_accum_kernel, so most terms leave through its direct-to-global branch
+    (test_p2i_edges.test_crowded_regions_overflow_the_hash_table asserts that on the oracle's ids).  S = 40: partial
+    regions; S = 43: partial 8 x 8 tiles as well.  The bounds are those of test_p2i_max_backward_regimes; the forward that produced
+    the ids is held to the oracle as well."""
+    import p2i_cases as pc
+    from sparenet_amd.cuda.p2i_op import ext
+    from test_p2i import _close_maps
+
+    case = pc.crowded(S, C)
+    B = pc.CROWDED_BATCH
+    pts, feat, bi = (np.array(a) for a in case[:3])
+    seed = 9000 + 100 * S + 10 * C + _SEEDS[regime]
+    gp, gf, gb, og, ids = _run_p2i_max(pts, feat, bi, B, S, C, radii, image_major, "multi", regime, seed, dev)
+    _p2i_max_check(og, ids, pts, feat, radii, gp, gf, (regime, S, C, radii, image_major))
+    ref_bg = np.where(ids < 0, og.astype(np.float64), 0.0).sum(0)
+    bg_bound = len(radii) * EPS * np.where(ids < 0, np.abs(og.astype(np.float64)), 0.0).sum(0)
+    _assert_regime(gb, ref_bg, bg_bound, (regime, S, C, radii, "background"))
+    again = _run_p2i_max(pts, feat, bi, B, S, C, radii, image_major, "multi", regime, seed, dev)
+    for a, b in zip((gp, gf, gb), again[:3]):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "two backward calls differ"
+    out, fids = ext.p2i_max_forward_multi_gpu(_t(pts, dev), _t(feat, dev), _t(bi, dev), _t(np.array(case.bg), dev), 0, radii,
+                                              image_major=image_major)
+    if image_major:
+        out, fids = out.transpose(0, 1), fids.transpose(0, 1)
+    assert np.array_equal(fids.cpu().numpy(), ids)
+    for r, R in enumerate(radii):
+        o, i = _crowded_oracle(S, C, R)
+        _close_maps(out[r].cpu().numpy(), ids[r], o, i, f"crowded S={S} C={C} R={R}", pts, feat, case.bg, R)
 
 
 # ----------------------------------------------------------------------------------------------- p2i sum
