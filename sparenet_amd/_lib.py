@@ -1,8 +1,12 @@
-"""ctypes binding of libsparenet_hip.so (the C ABI declared in include/sparenet_hip.h).
+"""ctypes binding of libsparenet_hip.so (the C ABI declared in include/sparenet_hip.h and, for the operators added
+after the reference's own, in include/sparenet_hip_ext.h).
 
-The header is the single description of a call: `prototypes()` parses it, `lib()` derives the ctypes signatures and
+A header is the single description of a call: `prototypes()` parses it, `lib()` derives the ctypes signatures and
 one prepared parameter list per function from that parse, and `call()` / `workspace()` are the one path on which
 Python values become C arguments -- checked against the declared pointee type, under the declared parameter name.
+`ext_call()` / `ext_workspace()` are the same path for the functions of the extension header, which are bound into a
+registry of their own: the main header's function list is pinned by the test suite, so new entry points are declared
+in the second header and reached by these two names.
 
 There is deliberately NO fallback: if the HIP library or its header is missing, or a tensor is not a contiguous
 CUDA(ROCm) tensor of the declared dtype, these helpers raise.  PyTorch is used only for device memory and streams.
@@ -17,8 +21,10 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsparenet_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sparenet_hip.h")
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sparenet_hip_ext.h")
 _lib = None
 _calls = {}     # name -> (ctypes function, prepared parameters, has a trailing stream, int result is a status code)
+_ext_calls = {}     # the same for the functions of the extension header
 
 SN_EINVAL = -22
 
@@ -89,35 +95,37 @@ def lib():
             raise SparenetHipError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` or `make -C sparenet_amd/csrc`. sparenet_amd has no CPU fallback.")
-        if not os.path.isfile(HEADER_PATH):
-            raise SparenetHipError(
-                f"{HEADER_PATH} not found: the header is the description of every call into {LIB_PATH} (argument "
-                "types, names and counts); the library is not loaded without it.")
+        for header in (HEADER_PATH, EXT_HEADER_PATH):
+            if not os.path.isfile(header):
+                raise SparenetHipError(
+                    f"{header} not found: the header is the description of every call into {LIB_PATH} (argument "
+                    "types, names and counts); the library is not loaded without it.")
         L = ctypes.CDLL(LIB_PATH)
         got = L.sn_abi_version()
         if got != EXPECTED_ABI:
             raise SparenetHipError(
                 f"{LIB_PATH} implements C ABI version {got}, this Python side needs {EXPECTED_ABI}: rebuild the "
                 "library (`make -C sparenet_amd/csrc`)")
-        _calls.clear()
-        for name, (ret, params) in prototypes().items():
-            fn = getattr(L, name, None)
-            if fn is None:          # a missing export is test_abi's finding, not a load-time failure
-                continue
-            fn.restype = _RETURNS[ret]
-            fn.argtypes = [(ctypes.c_char_p if p.ctype == "char" else ctypes.c_void_p) if p.pointer
-                           else _SCALARS[p.ctype] for p in params]
-            # an int function WITH parameters returns a status code; one without (sn_wait_policy, sn_emd_mode,
-            # sn_device_status ...) is a query whose number goes back to the caller
-            _calls[name] = (fn,) + _prepare(params) + (ret == "int" and bool(params),)
+        for registry, header in ((_calls, HEADER_PATH), (_ext_calls, EXT_HEADER_PATH)):
+            registry.clear()
+            for name, (ret, params) in prototypes(header).items():
+                fn = getattr(L, name, None)
+                if fn is None:          # a missing export is test_abi's finding, not a load-time failure
+                    continue
+                fn.restype = _RETURNS[ret]
+                fn.argtypes = [(ctypes.c_char_p if p.ctype == "char" else ctypes.c_void_p) if p.pointer
+                               else _SCALARS[p.ctype] for p in params]
+                # an int function WITH parameters returns a status code; one without (sn_wait_policy, sn_emd_mode,
+                # sn_device_status ...) is a query whose number goes back to the caller
+                registry[name] = (fn,) + _prepare(params) + (ret == "int" and bool(params),)
         _lib = L
     return _lib
 
 
 def signature(name):
-    """Names of the arguments `call(name, ...)` takes, in order."""
+    """Names of the arguments `call(name, ...)` (or `ext_call(name, ...)`) takes, in order."""
     lib()
-    return [step[1] for step in _calls[name][1]]
+    return [step[1] for step in (_calls.get(name) or _ext_calls[name])[1]]
 
 
 def check(code, what):
@@ -168,12 +176,22 @@ def call(name, *args, host=False):
     where that is allowed) or a host ctypes array of that element type; integers must be integral.  All device tensors
     must share one device, and the call runs under it.  A status code goes through check(); size_t / long long
     functions and parameterless queries return their number."""
-    spec = _calls.get(name)
+    return _invoke(_calls, HEADER_PATH, name, args, host)
+
+
+def ext_call(name, *args, host=False):
+    """`call` for a function declared in include/sparenet_hip_ext.h: the same conversion, checks and result."""
+    return _invoke(_ext_calls, EXT_HEADER_PATH, name, args, host)
+
+
+def _invoke(registry, header, name, args, host):
+    """The body of call / ext_call: `registry` holds what lib() prepared from `header`."""
+    spec = registry.get(name)
     if spec is None:
         lib()
-        spec = _calls.get(name)
+        spec = registry.get(name)
         if spec is None:
-            raise SparenetHipError(f"{name} is not declared in {HEADER_PATH} or not exported by {LIB_PATH}")
+            raise SparenetHipError(f"{name} is not declared in {header} or not exported by {LIB_PATH}")
     fn, steps, has_stream, is_status = spec
     if len(args) != len(steps):
         raise TypeError(f"{name} takes {len(steps)} arguments ({', '.join(s[1] for s in steps)}), got {len(args)}")
@@ -233,8 +251,17 @@ def workspace(size_export, like, *shape):
     """The scratch buffer of an op: `size_export(*shape)` is asked under `like`'s device (some layouts depend on its
     compute-unit count), and a uint8 tensor of that size -- at least one byte, so that it has an address -- is
     allocated there.  `call` passes the exported size, not the tensor's."""
+    return _sized(call, size_export, like, shape)
+
+
+def ext_workspace(size_export, like, *shape):
+    """`workspace` for a size export declared in include/sparenet_hip_ext.h."""
+    return _sized(ext_call, size_export, like, shape)
+
+
+def _sized(ask, size_export, like, shape):
     with torch.cuda.device_of(like):
-        nbytes = call(size_export, *shape)
+        nbytes = ask(size_export, *shape)
         return Workspace(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=like.device), nbytes)
 
 

@@ -22,47 +22,23 @@
 //   * both directions (1->2 and 2->1) run in ONE launch; blocks that share a
 //     target cloud are mapped to the same XCD (block id % 8) so the cloud's
 //     196 KB stay in one L2.
+#include "chamfer_tile.hpp"
 #include "common.hpp"
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
+// the distance expression, the min3 tree's element and the LDS tile layout are shared with set_chamfer.hip
+using sn::ct::f2;
+using sn::ct::dist1;
+using sn::ct::dist2;
+using sn::ct::min3;
+using sn::ct::kChunk;
+using sn::ct::kThreads;
+using sn::ct::kTile;
+using sn::ct::kTileF4;
 
-constexpr int kThreads = 256;
 constexpr int kQPL = 4;                  // queries per lane
 constexpr int kQPB = kThreads * kQPL;    // queries per block
-constexpr int kChunk = 8;                // targets per arg-min chunk
-constexpr int kTile = 1024;              // targets per LDS tile
-constexpr int kTileF4 = kTile / kChunk * 6;  // float4 slots per tile
-
-__device__ __forceinline__ float min3(float a, float b, float c) {
-  return __builtin_fminf(__builtin_fminf(a, b), c);
-}
-
-// d = (dx*dx + dy*dy) + dz*dz, two queries at once, no contraction
-__device__ __forceinline__ f2 dist2(float tx, float ty, float tz, f2 qx, f2 qy, f2 qz) {
-#pragma clang fp contract(off)
-  const f2 dx = tx - qx;
-  const f2 dy = ty - qy;
-  const f2 dz = tz - qz;
-  const f2 xx = dx * dx;
-  const f2 yy = dy * dy;
-  const f2 zz = dz * dz;
-  const f2 s = xx + yy;
-  return s + zz;
-}
-
-__device__ __forceinline__ float dist1(float tx, float ty, float tz, float qx, float qy, float qz) {
-#pragma clang fp contract(off)
-  const float dx = tx - qx;
-  const float dy = ty - qy;
-  const float dz = tz - qz;
-  const float xx = dx * dx;
-  const float yy = dy * dy;
-  const float zz = dz * dz;
-  const float s = xx + yy;
-  return s + zz;
-}
 
 // a cloud's point count from lengths[b], held to [0, width] so that no value a caller uploads can address outside the
 // cloud's rows
@@ -162,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void chamfer_fwd_kernel(
     for (int i = 0; i < kLd; ++i) {
       const int e = i * kThreads + tid;
       const int k = e / 3, comp = e - k * 3;
-      lds[(k >> 3) * 24 + comp * 8 + (k & 7)] = stage[i];
+      lds[sn::ct::tile_slot(k, comp)] = stage[i];
     }
   };
 

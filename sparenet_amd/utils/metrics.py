@@ -16,6 +16,7 @@ import torch
 from sparenet_amd.cuda.chamfer_distance.chamfer_distance import ChamferDistanceFunction
 from sparenet_amd.cuda.emd.emd_general import emd_general
 from sparenet_amd.cuda.emd.emd_module import emdModule
+from sparenet_amd.utils.set_metrics import set_metrics  # noqa: F401  (MMD-CD, COV-CD, 1-NNA-CD of two SETS of clouds)
 
 
 def f_score_from_chamfer(dist1, dist2, th=0.01):
