@@ -6,13 +6,16 @@ one prepared parameter list per function from that parse, and `call()` / `worksp
 Python values become C arguments -- checked against the declared pointee type, under the declared parameter name.
 `ext_call()` / `ext_workspace()` are the same path for the functions of the extension header, which are bound into a
 registry of their own: the main header's function list is pinned by the test suite, so new entry points are declared
-in the second header and reached by these two names.
+in the second header and reached by these two names.  That header's list is pinned in turn, so a later group of entry
+points has a header of its own, include/sparenet_hip_ext_<topic>.h: `lib()` binds each of them into a registry per
+topic, and `topic_call(topic, name, ...)` is the same path for those.
 
 There is deliberately NO fallback: if the HIP library or its header is missing, or a tensor is not a contiguous
 CUDA(ROCm) tensor of the declared dtype, these helpers raise.  PyTorch is used only for device memory and streams.
 """
 import collections
 import ctypes
+import glob
 import os
 import re
 
@@ -25,6 +28,7 @@ EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sparenet_hip_
 _lib = None
 _calls = {}     # name -> (ctypes function, prepared parameters, has a trailing stream, int result is a status code)
 _ext_calls = {}     # the same for the functions of the extension header
+_topic_calls = {}   # topic -> the same for the functions of include/sparenet_hip_ext_<topic>.h
 
 SN_EINVAL = -22
 
@@ -68,6 +72,12 @@ def prototypes(path=None):
     return out
 
 
+def topic_headers():
+    """{topic: path} of every include/sparenet_hip_ext_<topic>.h next to the main header."""
+    paths = sorted(glob.glob(os.path.join(os.path.dirname(HEADER_PATH), "sparenet_hip_ext_*.h")))
+    return {os.path.basename(p)[len("sparenet_hip_ext_"):-2]: p for p in paths}
+
+
 def _prepare(params):
     """The parameters `call` takes for a declared parameter list, as (kind, name, dtype, element type) -- without the
     trailing `void *stream`, and with `void *workspace, size_t workspace_bytes` as one -- and whether there is a stream."""
@@ -106,7 +116,9 @@ def lib():
             raise SparenetHipError(
                 f"{LIB_PATH} implements C ABI version {got}, this Python side needs {EXPECTED_ABI}: rebuild the "
                 "library (`make -C sparenet_amd/csrc`)")
-        for registry, header in ((_calls, HEADER_PATH), (_ext_calls, EXT_HEADER_PATH)):
+        _topic_calls.clear()
+        topics = [(_topic_calls.setdefault(topic, {}), header) for topic, header in topic_headers().items()]
+        for registry, header in [(_calls, HEADER_PATH), (_ext_calls, EXT_HEADER_PATH)] + topics:
             registry.clear()
             for name, (ret, params) in prototypes(header).items():
                 fn = getattr(L, name, None)
@@ -123,9 +135,13 @@ def lib():
 
 
 def signature(name):
-    """Names of the arguments `call(name, ...)` (or `ext_call(name, ...)`) takes, in order."""
+    """Names of the arguments `call(name, ...)` (or `ext_call(name, ...)`, `topic_call(topic, name, ...)`) takes, in
+    order."""
     lib()
-    return [step[1] for step in (_calls.get(name) or _ext_calls[name])[1]]
+    for registry in [_calls, _ext_calls] + list(_topic_calls.values()):
+        if name in registry:
+            return [step[1] for step in registry[name][1]]
+    raise KeyError(name)
 
 
 def check(code, what):
@@ -182,6 +198,16 @@ def call(name, *args, host=False):
 def ext_call(name, *args, host=False):
     """`call` for a function declared in include/sparenet_hip_ext.h: the same conversion, checks and result."""
     return _invoke(_ext_calls, EXT_HEADER_PATH, name, args, host)
+
+
+def topic_call(topic, name, *args, host=False):
+    """`call` for a function declared in include/sparenet_hip_ext_<topic>.h: the same conversion, checks and result."""
+    if topic not in _topic_calls:
+        lib()
+        if topic not in _topic_calls:
+            raise SparenetHipError(f"no header include/sparenet_hip_ext_{topic}.h next to {HEADER_PATH}")
+    header = os.path.join(os.path.dirname(HEADER_PATH), f"sparenet_hip_ext_{topic}.h")
+    return _invoke(_topic_calls[topic], header, name, args, host)
 
 
 def _invoke(registry, header, name, args, host):

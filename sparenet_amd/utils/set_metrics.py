@@ -1,7 +1,8 @@
 """The three set-level metrics published beside FPD for point-cloud generators and completion GANs, with the Chamfer
 distance between clouds: minimum matching distance (MMD-CD), coverage (COV-CD) and 1-nearest-neighbour accuracy
 (1-NNA-CD).  All three are read off the matrices of Chamfer distances between every generated and every reference
-cloud (sparenet_amd.cuda.set_distance.chamfer_matrix).
+cloud (sparenet_amd.cuda.set_distance.chamfer_matrix); `set_metrics(..., with_emd=True)` adds the same three on the
+matrices of auction EMDs (emd_matrix): MMD-EMD, COV-EMD and 1-NNA-EMD.
 
 The metric functions are plain torch on float64 matrices and work on any device, CPU included; only `set_metrics`
 itself, which computes the matrices, needs the GPU.  Ties are resolved to the LOWEST index, explicitly: torch.argmin
@@ -66,15 +67,27 @@ def one_nn_accuracy(cd_gg, cd_gr, cd_rr):
     return _ratio((is_ref[nearest] == is_ref).sum(), g + r)
 
 
-def set_metrics(gen, ref, cd_rr=None):
+def set_metrics(gen, ref, cd_rr=None, with_emd=False, emd_eps=0.005, emd_iters=50, emd_rr=None):
     """gen [G, n, 3], ref [R, m, 3] (contiguous fp32 CUDA tensors) -> {"MMD-CD", "COV-CD", "1-NNA-CD"}, float64 scalars
     on the clouds' device, from three chamfer_matrix calls.  `cd_rr` takes the reference set's own matrix
-    (chamfer_matrix(ref, ref)) where it has been computed before: it is the same for every checkpoint."""
-    from sparenet_amd.cuda.set_distance import chamfer_matrix
+    (chamfer_matrix(ref, ref)) where it has been computed before: it is the same for every checkpoint.
+    with_emd: also {"MMD-EMD", "COV-EMD", "1-NNA-EMD"}, the same three metrics on the auction EMD between the clouds
+    (sparenet_amd.cuda.set_distance.emd_matrix with emd_eps and emd_iters; `emd_rr` takes emd_matrix(ref, ref, ...)).
+    An EMD matrix of a set against itself is not symmetric (an auction is directed); the 1-NN classifier reads a
+    reference cloud's distances to the generated clouds off the transposed generated x reference matrix, as for CD."""
+    from sparenet_amd.cuda.set_distance import chamfer_matrix, emd_matrix
 
     cd_gr = chamfer_matrix(gen, ref)
     cd_gg = chamfer_matrix(gen, gen)
     if cd_rr is None:
         cd_rr = chamfer_matrix(ref, ref)
-    return {"MMD-CD": minimum_matching_distance(cd_gr), "COV-CD": coverage(cd_gr),
-            "1-NNA-CD": one_nn_accuracy(cd_gg, cd_gr, cd_rr)}
+    out = {"MMD-CD": minimum_matching_distance(cd_gr), "COV-CD": coverage(cd_gr),
+           "1-NNA-CD": one_nn_accuracy(cd_gg, cd_gr, cd_rr)}
+    if with_emd:
+        emd_gr = emd_matrix(gen, ref, emd_eps, emd_iters)
+        emd_gg = emd_matrix(gen, gen, emd_eps, emd_iters)
+        if emd_rr is None:
+            emd_rr = emd_matrix(ref, ref, emd_eps, emd_iters)
+        out.update({"MMD-EMD": minimum_matching_distance(emd_gr), "COV-EMD": coverage(emd_gr),
+                    "1-NNA-EMD": one_nn_accuracy(emd_gg, emd_gr, emd_rr)})
+    return out
