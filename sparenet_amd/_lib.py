@@ -8,7 +8,10 @@ Python values become C arguments -- checked against the declared pointee type, u
 registry of their own: the main header's function list is pinned by the test suite, so new entry points are declared
 in the second header and reached by these two names.  That header's list is pinned in turn, so a later group of entry
 points has a header of its own, include/sparenet_hip_ext_<topic>.h: `lib()` binds each of them into a registry per
-topic, and `topic_call(topic, name, ...)` is the same path for those.
+topic, and `topic_call(topic, name, ...)` is the same path for those.  The set of topic headers is pinned as well, so an
+operator added after them declares its entry points in include/ops/<name>.h: `lib()` binds every header of that
+directory into a registry per file name, `op_call(name_of_header, name, ...)` / `op_workspace(...)` are the same path
+for those, and the next operator adds a header there and nothing here.
 
 There is deliberately NO fallback: if the HIP library or its header is missing, or a tensor is not a contiguous
 CUDA(ROCm) tensor of the declared dtype, these helpers raise.  PyTorch is used only for device memory and streams.
@@ -29,6 +32,7 @@ _lib = None
 _calls = {}     # name -> (ctypes function, prepared parameters, has a trailing stream, int result is a status code)
 _ext_calls = {}     # the same for the functions of the extension header
 _topic_calls = {}   # topic -> the same for the functions of include/sparenet_hip_ext_<topic>.h
+_op_calls = {}      # stem -> the same for the functions of include/ops/<stem>.h
 
 SN_EINVAL = -22
 
@@ -78,6 +82,12 @@ def topic_headers():
     return {os.path.basename(p)[len("sparenet_hip_ext_"):-2]: p for p in paths}
 
 
+def op_headers():
+    """{stem: path} of every include/ops/<stem>.h: one header per operator added after the pinned ones."""
+    paths = sorted(glob.glob(os.path.join(os.path.dirname(HEADER_PATH), "ops", "*.h")))
+    return {os.path.basename(p)[:-2]: p for p in paths}
+
+
 def _prepare(params):
     """The parameters `call` takes for a declared parameter list, as (kind, name, dtype, element type) -- without the
     trailing `void *stream`, and with `void *workspace, size_t workspace_bytes` as one -- and whether there is a stream."""
@@ -118,7 +128,9 @@ def lib():
                 "library (`make -C sparenet_amd/csrc`)")
         _topic_calls.clear()
         topics = [(_topic_calls.setdefault(topic, {}), header) for topic, header in topic_headers().items()]
-        for registry, header in [(_calls, HEADER_PATH), (_ext_calls, EXT_HEADER_PATH)] + topics:
+        _op_calls.clear()
+        ops = [(_op_calls.setdefault(stem, {}), header) for stem, header in op_headers().items()]
+        for registry, header in [(_calls, HEADER_PATH), (_ext_calls, EXT_HEADER_PATH)] + topics + ops:
             registry.clear()
             for name, (ret, params) in prototypes(header).items():
                 fn = getattr(L, name, None)
@@ -135,10 +147,10 @@ def lib():
 
 
 def signature(name):
-    """Names of the arguments `call(name, ...)` (or `ext_call(name, ...)`, `topic_call(topic, name, ...)`) takes, in
-    order."""
+    """Names of the arguments `call(name, ...)` (or `ext_call(name, ...)`, `topic_call(topic, name, ...)`,
+    `op_call(stem, name, ...)`) takes, in order."""
     lib()
-    for registry in [_calls, _ext_calls] + list(_topic_calls.values()):
+    for registry in [_calls, _ext_calls] + list(_topic_calls.values()) + list(_op_calls.values()):
         if name in registry:
             return [step[1] for step in registry[name][1]]
     raise KeyError(name)
@@ -208,6 +220,21 @@ def topic_call(topic, name, *args, host=False):
             raise SparenetHipError(f"no header include/sparenet_hip_ext_{topic}.h next to {HEADER_PATH}")
     header = os.path.join(os.path.dirname(HEADER_PATH), f"sparenet_hip_ext_{topic}.h")
     return _invoke(_topic_calls[topic], header, name, args, host)
+
+
+def _op_registry(stem):
+    """(registry, header path) of include/ops/<stem>.h."""
+    if stem not in _op_calls:
+        lib()
+        if stem not in _op_calls:
+            raise SparenetHipError(f"no header include/ops/{stem}.h next to {HEADER_PATH}")
+    return _op_calls[stem], os.path.join(os.path.dirname(HEADER_PATH), "ops", f"{stem}.h")
+
+
+def op_call(stem, name, *args, host=False):
+    """`call` for a function declared in include/ops/<stem>.h: the same conversion, checks and result."""
+    registry, header = _op_registry(stem)
+    return _invoke(registry, header, name, args, host)
 
 
 def _invoke(registry, header, name, args, host):
@@ -283,6 +310,11 @@ def workspace(size_export, like, *shape):
 def ext_workspace(size_export, like, *shape):
     """`workspace` for a size export declared in include/sparenet_hip_ext.h."""
     return _sized(ext_call, size_export, like, shape)
+
+
+def op_workspace(stem, size_export, like, *shape):
+    """`workspace` for a size export declared in include/ops/<stem>.h."""
+    return _sized(lambda name, *dims: op_call(stem, name, *dims), size_export, like, shape)
 
 
 def _sized(ask, size_export, like, shape):
