@@ -148,6 +148,11 @@ int sn_chamfer_backward_host(const float *xyz1, const float *xyz2,
  * workgroups own a cloud and synchronise through bounded, placement-independent barriers).
  * Environment: SN_EMD_CHECK=1 makes the call synchronise and fail if a barrier timed out (under SN_WAIT_RECOVER: if
  * a time-out survived the recovery pass).
+ * SN_EMD_RETIRE (read once per process; results are bit-identical for every value): the unassigned bidders per
+ * workgroup (cloud total / workgroups of the team) from which on every workgroup of a team's LAST cloud ends waves
+ * 8-15 and frees half of its compute unit's registers for kernels of other streams -- unset: 80, and only in launches
+ * whose teams all have a cloud; 0: never; a positive value: that threshold in every launch; -k-1: at the top of
+ * iteration k whatever the cloud looks like (tests and experiments).  Contested and far clouds never retire on their own.
  * stats (optional device pointer, may be NULL): 2 x int64, zeroed by the caller
  *   stats[0] += sum over iterations and batch of unassigned_count * n
  *               (effective pair evaluations); stats[1] += iterations that had

@@ -46,10 +46,25 @@
 //   * Round 6: in the per-bidder scan a box of 16 (or 256) targets is tested against a reach computed from the box's OWN
 //     price bound (box_within_priced); on contested clouds that bound is the smallest price the box holds, refreshed
 //     in LDS every fourth contested iteration -- a far bidder no longer lists the expensive near-side blocks.
+//   * Round 7: WAVE RETIREMENT.  From iteration ~12 of a uniform cloud a workgroup has a hundred bidders left and an
+//     iteration is one to three passes of a latency chain, while its 16 waves of 128 VGPRs keep every other kernel off
+//     the CU.  In the team's last cloud, once the cloud is sparse (at most G x kRetire bidders, not contested, not far),
+//     waves 8-15 of every workgroup END: registers are allocated per wave and s_barrier counts the waves that are left,
+//     so half of every CU's register file goes back, and the kernels of the other streams flow in for the rest of
+//     the call (kernel trace, 32 clouds: the renderer's first kernel used to wait 1.85 ms for the auction's end; now
+//     its whole chain starts ~1.3 ms into the 2.1 ms window and the binned gather spends its first 0.5 ms beside the
+//     auction).  The iteration body exists twice, templated on the wave count (`iterate` in auction_body); thread 0's
+//     protocol and the fixed thread ids do not move, results are bit-identical (who serves a bidder never enters one).
+//     The tail at 8 waves serves 32 bidders per scan pass instead of 64: the call alone gets 0.13 ms longer (2.08 ->
+//     2.21), the step 0.2 ms shorter (4.22-4.30 -> 4.03 ms, profiles/r07_a_headline.txt).  For the co-runners to fit,
+//     the LDS went from 151 to 108 KB (AuctionLds: the two bid forms share their bytes): with 151 KB the renderer's
+//     binning kernel (33 KB) stayed out and the step LOST 0.3 ms.  s_setprio(2) on the surviving waves: 4.08 / 4.08
+//     against 4.08 ms per step, not kept.  DESIGN.md section 5, "EMD in round 7".
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "cloud_sort.hpp"
 #include "common.hpp"
@@ -319,8 +334,20 @@ struct BidOut {
 
 constexpr int kBidWaves = 16;  // waves per workgroup
 constexpr int kBidThreads = kBidWaves * 64;
-constexpr int kWgPerCu = 1;    // 16 waves of 128 VGPRs fill a CU's register files: one workgroup per CU
-constexpr int kStash = kBidThreads;  // list slots whose bid is handed to the award phase through LDS
+constexpr int kWgPerCu = 1;    // 16 waves of 128 VGPRs fill a CU's register files: one workgroup per CU (until it retires half)
+constexpr int kStash = kBidThreads;  // list slots whose bid is handed to the award phase through LDS (a retired
+                                     // workgroup keeps all of them: thread t then serves the slots t and t + 512)
+// Retirement: the waves a workgroup keeps once its cloud is sparse (the fixed thread ids of the iteration body --
+// tid < 64 + kRankBins, tid == kRankBins -- need five waves; the compaction and bid_group's split want a power of two)
+constexpr int kRetWaves = 8;
+constexpr int kRetThreads = kRetWaves * 64;
+static_assert(kRetThreads >= 64 + kRankBins + 1 && kBidWaves % kRetWaves == 0, "fixed thread ids must survive retirement");
+// bidders per workgroup (cloud total / G) from which on a workgroup retires (SN_EMD_RETIRE).  Step of bench.py at 32
+// clouds, ms: never 4.26-4.28 | 32: 4.27 | 48: 4.21-4.29 | 64: 4.12-4.15 | 80: 4.07 | 96: 4.08-4.09 | 112: 4.14 | 128: 4.17-4.19 |
+// 160: 4.25 | 256: 4.34 | 512: 4.44 (profiles/r07_a_retire_sweep.txt): too early and the 8-wave tail costs more than
+// the renderer gains beside it, too late and there is no tail left to share.
+constexpr int kRetire = 80;
+constexpr int kIterDone = -1, kIterBailed = -2;  // what a pass over the iterations returns besides an iteration number
 
 // What the award phase needs to know about the bid of list slot u (written by the wave that emits the bid, read
 // after the team barrier by thread u): saves the llist -> bid -> rec chain of dependent coherent loads.
@@ -1010,6 +1037,8 @@ struct ScanCand {  // one round of a quarter wave: lane c holds target c of each
 };
 
 
+// kWaves: the waves of the workgroup that take part (16, or 8 once a workgroup has retired half of them: see the kernel)
+template <int kWaves>
 __device__ __forceinline__ void bid_scan(const BidCtx &c, ScanLds &SL, const int *lst, int count, int wave,
                                          int lane) {
   const int row = lane >> 4, col = lane & 15;
@@ -1023,7 +1052,7 @@ __device__ __forceinline__ void bid_scan(const BidCtx &c, ScanLds &SL, const int
   for (int u0 = 0; u0 < count;) {
     // T quarter waves per bidder: with few bidders left a bidder's superblocks are dealt out to 2 or 4 quarters
     const int rem = count - u0;
-    constexpr int kQuarters = kBidWaves * 4;  // quarter waves of the workgroup (qd below runs over them)
+    constexpr int kQuarters = kWaves * 4;  // quarter waves of the workgroup (qd below runs over them)
     const int tsh = rem <= kQuarters / 4 ? 2 : (rem <= kQuarters / 2 ? 1 : 0), T = 1 << tsh;  // uniform in the workgroup
     const int qd = wave * 4 + row;
     const int u = u0 + (qd >> tsh), part = qd & (T - 1);
@@ -1267,6 +1296,8 @@ struct AuctionArgs {
   long long *dwords;
   int diag_m0;   // SN_EMD_DIAG_M0: the first of the eight workgroups of team 0 whose per-iteration times are recorded
   int scan_max;  // iterations with at most this many bidders in the workgroup take bid_scan (0: never)
+  int retire;    // > 0: a workgroup retires its upper waves once the cloud has at most G x this many bidders (not in a
+                 // contested or far regime); 0: never; -k-1: at the top of iteration k whatever the regime (tests)
   int prof;      // 1: record the execution window in the control block (sn_prof_enable)
   int skip_mode;     // contested-auction handling (outbid-skip + scan everywhere): 0 never, 1 when the lists say so (default), 2 always
   int spread_mode;   // interleaved rank split in scan iterations: 0 never, 1 default, 2 in every iteration
@@ -1276,15 +1307,25 @@ struct AuctionArgs {
 // The kernel's LDS, carved from the DYNAMIC segment on purpose: with a static 101 KB the compiler derives "one
 // workgroup per CU = 4 waves per SIMD" from the LDS size and hands every wave 128 VGPRs whatever the occupancy
 // attributes say.  Dynamic, the register budget is what emd_auction_kernel's attributes ask for.
+// The two bid forms never run in the same iteration of a workgroup, so the matrix-core search's tables and the scan's
+// copy of the box hierarchy SHARE their bytes: 108 KB instead of 151 KB, which leaves 52 KB of a CU's LDS to the
+// kernels that flow in beside a retired workgroup (the renderer's binning kernel needs 33 KB, the expansion penalty 14).
+// The boxes are copied when an iteration first takes the scan (`boxes_of` in auction_body) -- on uniform clouds once per
+// cloud, as before -- and the group locks are cleared again when a workgroup goes back to the matrix-core search.
 struct AuctionLds {
-  WaveTab tabs[kBidWaves];
-  GroupAcc gacc[kBidWaves];
+  union {
+    struct {
+      WaveTab tabs[kBidWaves];
+      GroupAcc gacc[kBidWaves];
+    } grp;
+    ScanLds scan;
+  };
   BidStash stash[kStash];
   int wsum[kBidWaves];
   int s_flag, s_ticket, s_stray, s_range[4], s_bins[kRankBins];
   int s_long, s_skipped;
-  ScanLds scan;
 };
+static_assert(sizeof(AuctionLds) <= 108 * 1024, "the auction's LDS must leave room for the kernels that run beside it");
 
 // (Round 4 also built this body a second time for 96 VGPRs per wave -- amdgpu_waves_per_eu(5, 5), a quarter of every
 // SIMD's registers left to co-resident launches -- selectable per call: with the quarter-wave scan the 96-register
@@ -1293,8 +1334,8 @@ struct AuctionLds {
 __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char auction_lds[];
   AuctionLds &L = *reinterpret_cast<AuctionLds *>(auction_lds);
-  WaveTab *tabs = L.tabs;
-  GroupAcc *gacc = L.gacc;
+  WaveTab *tabs = L.grp.tabs;
+  GroupAcc *gacc = L.grp.gacc;
   BidStash *stash = L.stash;
   int *wsum = L.wsum;
   int &s_flag = L.s_flag, &s_ticket = L.s_ticket, &s_stray = L.s_stray;
@@ -1353,9 +1394,9 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   // not look like a result: the clouds this team had not finished get NaN distances and -1 assignments, the
   // device's sticky word makes the next sn_emd_* call fail (the reference returns an error code there,
   // emd_cuda.cu:276-281).  The NaN / -1 rows are also the marker the recovery pass of SN_WAIT_RECOVER looks for.
-  auto bail = [&](int b_from) {
+  auto bail = [&](int b_from, int nthr = kBidThreads) {  // nthr: the threads the workgroup still has (see retirement)
     for (int b = b_from; b < a.B; b += a.tg.teams)
-      for (int e = tid; e < n; e += kBidThreads) {
+      for (int e = tid; e < n; e += nthr) {
         a.dist[(size_t)b * n + e] = __builtin_nanf("");
         a.assignment[(size_t)b * n + e] = -1;
       }
@@ -1401,6 +1442,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
   BidOut bo = {a.ws.bid, a.ws.bid2, a.ws.rec, a.ws.max_inc, a.ws.head, loc, 0};
   unsigned *const note = a.ctl->bar + (size_t)(a.tg.teams + team) * 32 + kNoteWord;  // cont[2] of this team (see kNoteWord)
   int cloud_seq = 0;
+  int boxes_of = -1;  // the cloud whose boxes L.scan holds; -1: the bytes are the matrix-core search's tables, locks clear
   if (a.diag && m == 0 && tid == 0 && loc) atomicAdd(reinterpret_cast<unsigned long long *>(a.dwords) + 12, 1ull);  // teams on one XCD
 
   for (int b = team; b < a.B; b += a.tg.teams) {
@@ -1431,15 +1473,17 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
     const bool far = a.ws.far != nullptr && 4 * a.ws.far[b] > n;
     // bid_scan's copy of the cloud's box hierarchy (constant for the whole call)
     const bool scan_ok = a.scan_max > 0 && 4 * nsb <= kScanBlk;  // nsb % 16 == 0 (n % 1024 == 0)
-    if (scan_ok) {
-      __syncthreads();  // a team that serves several clouds: nobody still reads the previous cloud's boxes
+    // (copied when an iteration first takes the scan: the bytes are the matrix-core search's tables until then)
+    auto setup_boxes = [&](auto wtag) __attribute__((always_inline)) {
+      constexpr int kThr = decltype(wtag)::value * 64;
+      __syncthreads();  // nobody still uses the bytes (the previous iteration's search, the previous cloud's boxes)
       {
         const f4 *src = reinterpret_cast<const f4 *>(c.sbb);  // [n / 16] rows {lo x, lo y, lo z, hi x}, {hi y, hi z, -, -}
         f4 *dst = &L.scan.blk[0][0];
-        for (int i = tid; i < 8 * nsb; i += kBidThreads) dst[i] = src[i];
+        for (int i = tid; i < 8 * nsb; i += kThr) dst[i] = src[i];
       }
       __syncthreads();
-      for (int h = tid; h < (nsb >> 2); h += kBidThreads) {
+      for (int h = tid; h < (nsb >> 2); h += kThr) {
         f4 lo = L.scan.blk[16 * h][0], hi = L.scan.blk[16 * h][1];
         for (int q = 1; q < 16; ++q) {
           const f4 l2 = L.scan.blk[16 * h + q][0], h2 = L.scan.blk[16 * h + q][1];
@@ -1458,14 +1502,23 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
       // for a start -- prices only rise for eps >= 0, so it stays valid until an iteration refreshes it
       {
         const float amax0 = filter_target(0.f) + 9.5367431640625e-07f;
-        for (int i = tid; i < 4 * nsb; i += kBidThreads) L.scan.blk[i][1].z = amax0;
-        for (int h = tid; h < (nsb >> 2); h += kBidThreads) L.scan.hb[h][1].z = amax0;
+        for (int i = tid; i < 4 * nsb; i += kThr) L.scan.blk[i][1].z = amax0;
+        for (int h = tid; h < (nsb >> 2); h += kThr) L.scan.hb[h][1].z = amax0;
       }
       __syncthreads();
-    }
+    };
 
     int bmin_it = -1000;  // the iteration of the last refresh of the boxes' price bounds (see the bid phase)
-    for (int it = 0; it < a.iters; ++it) {
+    // RETIREMENT (see the kernel's header): only in the team's last cloud, so that it is one-way for the launch and the
+    // clouds before it -- box set-up included -- run at full width
+    const bool may_retire = a.retire != 0 && b + a.tg.teams >= a.B;
+    // The iterations it0 .. iters - 1 with kWaves waves per workgroup.  Returns kIterDone, kIterBailed (a barrier gave
+    // up: the workgroup has written its markers and leaves) or, from the full-width instantiation only, the iteration
+    // at whose top the workgroup retires its upper half: the caller lets those waves end and calls the kRetWaves
+    // instantiation with `resume`, which takes the split of that iteration from LDS where wave 0 left it.
+    auto iterate = [&](auto wtag, const int it0, const bool resume) __attribute__((always_inline)) -> int {
+    constexpr int kWaves = decltype(wtag)::value, kThr = kWaves * 64;
+    for (int it = it0; it < a.iters; ++it) {
       const int cur = it & 1;
       // (Round 4 measured a deterministic COST-weighted split here -- every bin weighted with the work bid_scan's
       // bidders of that bin needed in the previous iteration (groups of 256 targets within reach), so that skewed data
@@ -1492,7 +1545,8 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
       // atomics; the bidders' order inside a list never enters a result.
       const unsigned stamp = stamp0 + (unsigned)it + 1u;
       const bool last = it == a.iters - 1;
-      if (wave == 0) {  // lane l holds the bins (positions) 4 l .. 4 l + 3
+      const bool split_known = resume && it == it0;  // s_range holds this iteration's split already
+      if (wave == 0 && !split_known) {  // lane l holds the bins (positions) 4 l .. 4 l + 3
         const int2 lo2 = ldc2(a.ws.bins[cur] + b * kRankBins + 4 * lane);
         const int2 hi2 = ldc2(a.ws.bins[cur] + b * kRankBins + 4 * lane + 2);
         int contw = 0;
@@ -1553,10 +1607,13 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
           s_range[3] = (contested ? 1 : 0) | (spread ? 2 : 0);
         }
       }
-      __syncthreads();
+      if (!split_known) __syncthreads();
       const int U = s_range[0], p0 = s_range[1], R = s_range[2] * binsize;
       if (U == 0) break;  // every workgroup of the team reads the same value
       const bool contested = (s_range[3] & 1) != 0, spread = (s_range[3] & 2) != 0;
+      if constexpr (kWaves == kBidWaves) {  // the same answer in every wave of every workgroup of the team
+        if (may_retire && (a.retire < 0 ? it == -1 - a.retire : (!contested && !far && U <= G * a.retire))) return it;
+      }
       const int r0 = p0 * binsize;  // where the workgroup's list lives (by position: disjoint whatever the order)
       int *llist = llist_all + 2 * (o + r0);   // {index, rank} pairs
       if (m == 0 && tid == 0 && a.stats) {
@@ -1582,7 +1639,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
       {
         int base = 0;
         const int vec = R >> 2;
-        for (int w0 = 0; w0 < vec; w0 += kBidThreads) {
+        for (int w0 = 0; w0 < vec; w0 += kThr) {
           const int w = w0 + tid;
           int4 f = make_int4(0, 0, 0, 0);
           // word w of the workgroup's positions: position p0 + w / wpb, i.e. bin p (contiguous) or its transpose
@@ -1606,7 +1663,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
           if (lane == 63) wsum[wave] = incl;
           __syncthreads();
           int pos = base + incl - cnt, total = 0;
-          for (int wv = 0; wv < kBidWaves; ++wv) {
+          for (int wv = 0; wv < kWaves; ++wv) {
             if (wv < wave) pos += wsum[wv];
             total += wsum[wv];
           }
@@ -1658,6 +1715,11 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
         c.offsurf = contested || far;
         const int scan_max = ((contested || far) && a.scan_max > 0 && a.scan_max < kScanContested) ? kScanContested : a.scan_max;
         if (scan_ok && Um <= scan_max) {  // uniform in the workgroup: a quarter wave per bidder
+          if (boxes_of != b) {
+            setup_boxes(wtag);
+            boxes_of = b;
+            bmin_it = -1000;  // the price floor's bounds again: a contested iteration refreshes them at once
+          }
           if (contested && a.eps >= 0.f && it - bmin_it >= kBminEvery) {
             // CONTESTED clouds: every box's bound from the SMALLEST PRICE it holds now (prices do not move during a bid
             // phase).  A bidder there sits far from the surface, the near-side targets' prices have climbed, and with the
@@ -1667,7 +1729,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
             // low) while the untrained regime gained (31.2 -> 26.7): hence contested iterations only, and every fourth
             // one -- a bound from earlier, lower prices stays valid (eps >= 0: prices only rise).
             bmin_it = it;
-            for (int bq = tid; bq < 4 * nsb; bq += kBidThreads) {
+            for (int bq = tid; bq < 4 * nsb; bq += kThr) {
               const float2 *pp = c.pkc + 16 * bq;
               float pm = 3.0e38f;
 #pragma unroll 8
@@ -1675,23 +1737,30 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
               L.scan.blk[bq][1].z = filter_target(pm) + 9.5367431640625e-07f;
             }
             __syncthreads();
-            for (int h = tid; h < (nsb >> 2); h += kBidThreads) {
+            for (int h = tid; h < (nsb >> 2); h += kThr) {
               float mx = L.scan.blk[16 * h][1].z;
               for (int q = 1; q < 16; ++q) mx = __builtin_fmaxf(mx, L.scan.blk[16 * h + q][1].z);
               L.scan.hb[h][1].z = mx;
             }
             __syncthreads();
           } else if (a.eps < 0.f) {  // prices may fall: this iteration's price floor for every box
-            for (int i = tid; i < 4 * nsb; i += kBidThreads) L.scan.blk[i][1].z = c.a_max;
-            for (int h = tid; h < (nsb >> 2); h += kBidThreads) L.scan.hb[h][1].z = c.a_max;
+            for (int i = tid; i < 4 * nsb; i += kThr) L.scan.blk[i][1].z = c.a_max;
+            for (int h = tid; h < (nsb >> 2); h += kThr) L.scan.hb[h][1].z = c.a_max;
             __syncthreads();
           }
-          bid_scan(c, L.scan, llist, Um, wave, lane);
+          bid_scan<kWaves>(c, L.scan, llist, Um, wave, lane);
         } else {
+          if (boxes_of >= 0) {  // back from the scan (a contested turn, the next cloud): the tables' bytes held boxes
+            if (tid < kBidWaves) {  // wave 0; bid_group's first workgroup barrier lies between this and the locks' use
+              gacc[tid].lock = 0;
+              gacc[tid].arrived = 0;
+            }
+            boxes_of = -1;
+          }
           const int ngroups = (Um + 63) >> 6;
           int S = 1;
-          while (S < kBidWaves && S * 2 * ngroups <= kBidWaves) S *= 2;
-          const int gpb = kBidWaves / S;
+          while (S < kWaves && S * 2 * ngroups <= kWaves) S *= 2;
+          const int gpb = kWaves / S;
           const int seg = wave & (S - 1), gslot = wave / S;
           for (int q0 = 0; q0 < ngroups; q0 += gpb) {
             bid_group(c, tabs[wave], gacc[gslot], llist, Um, q0 + gslot, ngroups, S, seg, lane);
@@ -1702,8 +1771,8 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
       if (a.diag) __syncthreads();
       tick(6);
       if (!team_barrier(ts, &s_flag)) {
-        bail(b);
-        return;
+        bail(b, kThr);
+        return kIterBailed;
       }
       tick(7);
       // ---- award: GetMax (emd_cuda.cu:181-194) and Assign (:196-215) in one target-centric pass.
@@ -1725,7 +1794,7 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
           atomicAdd(&s_bins[rank / binsize], 1);
         };
         const int *rec = a.ws.rec + 4 * o;
-        for (int u = tid; u < Um; u += kBidThreads) {
+        for (int u = tid; u < Um; u += kThr) {
           int tgt, rank, inc_bits, nxt, jown;
           if (u < kStash) {
             const BidStash sb = stash[u];
@@ -1846,15 +1915,18 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
       if (a.diag) __syncthreads();
       tick(8);
       if (!team_barrier(ts, &s_flag)) {
-        bail(b);
-        return;
+        bail(b, kThr);
+        return kIterBailed;
       }
       tick(9);
     }
+    return kIterDone;
+    };
     // ---- distances of the final assignment (emd_cuda.cu:218-226), own slice of the bidder indices
-    {
+    auto distances = [&](auto wtag) __attribute__((always_inline)) {
 #pragma clang fp contract(off)
-      for (int e = rs0 + tid; e < rs0 + Rs; e += kBidThreads) {
+      constexpr int kThr = decltype(wtag)::value * 64;
+      for (int e = rs0 + tid; e < rs0 + Rs; e += kThr) {
         const int k = ldc(&a.assignment[o + e]);
         float d = 0.f;
         if (k >= 0) {
@@ -1864,8 +1936,25 @@ __device__ __forceinline__ void auction_body(const AuctionArgs &a) {
         }
         a.dist[o + e] = d;
       }
+    };
+    const int rc = iterate(std::integral_constant<int, kBidWaves>{}, 0, false);
+    if (rc == kIterBailed) return;
+    if (rc == kIterDone) {
+      distances(std::integral_constant<int, kBidWaves>{});
+      continue;  // a team that serves several clouds: the flags / lists of the next cloud are its own, nothing to wait for
     }
-    // a team that serves several clouds: the flags / lists of the next cloud are its own, nothing to wait for
+    // ---- retirement at the top of iteration rc.  Every wave has passed the workgroup barrier behind the split (and
+    // with it the team barrier that closed the previous iteration); nothing of the upper half is pending in LDS (the
+    // group locks, wsum and the bin counters are idle between iterations).  Its waves drain their stores and END: their
+    // registers and wave slots go back to the CU, the workgroup's barriers count the waves that are left.  Thread 0
+    // (team barriers, stamps), the fixed thread ids up to 64 + kRankBins and the LDS layout stay what they were.
+    if (wave >= kRetWaves) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      return;
+    }
+    if (iterate(std::integral_constant<int, kRetWaves>{}, rc, true) == kIterBailed) return;
+    distances(std::integral_constant<int, kRetWaves>{});
+    break;  // the team's last cloud (may_retire)
   }
   if (a.prof && tid == 0) atomicMax(&a.ctl->t_last, (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
@@ -2300,6 +2389,14 @@ extern "C" int sn_emd_forward(const float *xyz1, const float *xyz2, int b, int n
       args.scan_max = v < 0 ? 0 : v;
     }
     args.tg = team_geometry(b, cus * kWgPerCu, solo ? 1 : 64);
+    {  // retirement (see the kernel's header); once per process, per call under SN_KNOBS_PER_CALL=1
+      // The default retires only in launches whose teams ALL have a cloud: with fewer clouds than teams whole XCDs are
+      // free for the other streams anyway and the 8-wave tail only makes the call longer (4 clouds per GPU: 1.53-1.60
+      // -> 1.64-1.80 ms per step, 8 clouds: 1.91-1.93 -> 1.81-1.82, 16: unchanged; profiles/r07_a_strong_share.txt).
+      const char *e = SN_KNOB("SN_EMD_RETIRE");
+      const long r = e ? atol(e) : (b >= args.tg.teams ? kRetire : 0);
+      args.retire = (int)(r > (1 << 20) ? (1 << 20) : (r < -(1 << 20) ? -(1 << 20) : r));  // n <= 2^20: G x retire fits an int
+    }
     // the park knob (diag bit 3) parks a workgroup of a team-waiting launch; with teams of one workgroup that
     // workgroup would be a whole team and its cloud unwritten: under recover / nowait such launches ignore it
     args.diag = policy != SN_WAIT_FAIL && args.tg.G == 1 ? diag & ~8 : diag;
