@@ -1,0 +1,59 @@
+// block_scan.hpp -- the prefix sums every count / scan / fill chain needs (gfx950 only): the inclusive scan of a wave, and
+// the exclusive scan of a whole workgroup over a sequence of any length, taken in chunks of one value per thread with the
+// running total carried from chunk to chunk in LDS.
+//
+//   __shared__ alignas(16) sn::BlockScan<1024> scan;    // aligned: the wave sums are then read four words at a time
+//   scan.reset(start);                                  // the sum in front of the first value
+//   for (int base = 0; base < n; base += 1024) {
+//     const int i = base + threadIdx.x;
+//     const int v = i < n ? count[i] : 0;               // EVERY thread takes part in every chunk
+//     scan.chunk(v, [&](int exclusive) { if (i < n) start_of[i] = exclusive; });
+//   }
+//   ... scan.carry is start + the sum of all values, in every thread
+#pragma once
+#include "common.hpp"
+
+namespace sn {
+
+// inclusive prefix sum of v over the lanes of a wave
+__device__ __forceinline__ int wave_inclusive_scan(int v) {
+  const int lane = threadIdx.x & (kWave - 1);
+  for (int d = 1; d < kWave; d <<= 1) {
+    const int u = __shfl_up(v, d);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+
+// Lives in __shared__ memory of a one-dimensional workgroup of kThreads threads; all of them call reset and chunk.
+// The alignment belongs to the variable, not to the type: an aligned type would round these 68 bytes up to 80.
+template <int kThreads>
+struct BlockScan {
+  static_assert(kThreads % kWave == 0, "whole waves");
+  int wsum[kThreads / kWave];  // the sum of each wave of the chunk in flight
+  int carry;                   // the sum of everything in front of that chunk; after the last chunk, the total
+
+  // only thread 0's `start` counts.  Ends in a barrier.
+  __device__ __forceinline__ void reset(int start) {
+    if (threadIdx.x == 0) carry = start;
+    __syncthreads();
+  }
+
+  // body(exclusive prefix of this thread's v) runs between two barriers: it may overwrite what v was read from.  The
+  // inclusive prefix is exclusive + v.  Ends in a barrier, behind which carry includes the chunk.
+  template <class Body>
+  __device__ __forceinline__ void chunk(int v, Body &&body) {
+    const int tid = threadIdx.x;
+    const int incl = wave_inclusive_scan(v);
+    if ((tid & (kWave - 1)) == kWave - 1) wsum[tid / kWave] = incl;
+    __syncthreads();
+    int pre = carry;
+    for (int w = 0; w < tid / kWave; ++w) pre += wsum[w];
+    body(pre + incl - v);
+    __syncthreads();  // every thread has read carry and wsum
+    if (tid == kThreads - 1) carry = pre + incl;
+    __syncthreads();
+  }
+};
+
+}  // namespace sn

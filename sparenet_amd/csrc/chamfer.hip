@@ -22,6 +22,7 @@
 //   * both directions (1->2 and 2->1) run in ONE launch; blocks that share a
 //     target cloud are mapped to the same XCD (block id % 8) so the cloud's
 //     196 KB stay in one L2.
+#include "block_scan.hpp"
 #include "chamfer_tile.hpp"
 #include "common.hpp"
 
@@ -289,32 +290,20 @@ __global__ __launch_bounds__(256) void chamfer_bwd_count_kernel(const int *__res
 __global__ __launch_bounds__(1024) void chamfer_bwd_scan_kernel(int NM, const int *__restrict__ cnt,
                                                                int *__restrict__ off, int *__restrict__ fill,
                                                                int *__restrict__ longs) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
+  __shared__ alignas(16) sn::BlockScan<1024> scan;
   const int b = blockIdx.x, tid = threadIdx.x;
   const long o = (long)b * NM;
-  if (tid == 0) carry = 0;
-  __syncthreads();
+  scan.reset(0);
   for (int base = 0; base < NM; base += 1024) {
     const int i = base + tid;
     const int c = i < NM ? cnt[o + i] : 0;
-    int incl = c;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d);
-      if ((tid & 63) >= d) incl += v;
-    }
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int w = 0; w < (tid >> 6); ++w) pre += wsum[w];
-    if (i < NM) {
-      off[o + i] = pre + incl - c;
-      fill[o + i] = pre + incl - c;
-      if (c > kLongList) longs[1 + atomicAdd(&longs[0], 1)] = (int)(o + i);
-    }
-    __syncthreads();
-    if (tid == 1023) carry = pre + incl;
-    __syncthreads();
+    scan.chunk(c, [&](int start) {
+      if (i < NM) {
+        off[o + i] = start;
+        fill[o + i] = start;
+        if (c > kLongList) longs[1 + atomicAdd(&longs[0], 1)] = (int)(o + i);
+      }
+    });
   }
 }
 
@@ -356,8 +345,7 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_lists_kernel(const int *__re
                                                                const int *__restrict__ len1,
                                                                const int *__restrict__ len2) {
   extern __shared__ int lc[];  // N + M counters, later the fill cursors
-  __shared__ int wsum[16];
-  __shared__ int carry;
+  __shared__ alignas(16) sn::BlockScan<1024> scan;
   const int b = blockIdx.x, tid = threadIdx.x, NM = N + M;
   const long o = (long)b * NM;
   const int *i1 = idx1 + (long)b * N, *i2 = idx2 + (long)b * M;
@@ -365,32 +353,21 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_lists_kernel(const int *__re
   // a row that is a point of its cloud (every row of a dense batch)
   auto valid = [&](int e) { return !kRagged || (e >= N ? e - N < L.n2 : e < L.n1); };
   for (int i = tid; i < NM; i += 1024) lc[i] = 0;
-  if (tid == 0) carry = 0;
-  __syncthreads();
+  scan.reset(0);  // its barrier also stands behind the zeroed counters
   for (int e = tid; e < NM; e += 1024)
     if (valid(e)) atomicAdd(&lc[e >= N ? clamp_idx(i2[e - N], L.n1) : N + clamp_idx(i1[e], L.n2)], 1);
   __syncthreads();
   for (int base = 0; base < NM; base += 1024) {
     const int i = base + tid;
     const int c = i < NM ? lc[i] : 0;
-    int incl = c;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d);
-      if ((tid & 63) >= d) incl += v;
-    }
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int w = 0; w < (tid >> 6); ++w) pre += wsum[w];
-    if (i < NM) {
-      cnt[o + i] = c;
-      off[o + i] = pre + incl - c;
-      lc[i] = pre + incl - c;
-      if (c > kLongList) longs[1 + atomicAdd(&longs[0], 1)] = (int)(o + i);
-    }
-    __syncthreads();
-    if (tid == 1023) carry = pre + incl;
-    __syncthreads();
+    scan.chunk(c, [&](int start) {
+      if (i < NM) {
+        cnt[o + i] = c;
+        off[o + i] = start;
+        lc[i] = start;
+        if (c > kLongList) longs[1 + atomicAdd(&longs[0], 1)] = (int)(o + i);
+      }
+    });
   }
   for (int e = tid; e < NM; e += 1024) {
     if (!valid(e)) continue;

@@ -6,6 +6,7 @@
 // inside a cell is arbitrary).  The scatter used to be a second, grid-wide launch with one global atomic per
 // point (23 us next to the count kernel's 24 at 32 x 16384 points; together now 30).
 #pragma once
+#include "block_scan.hpp"
 #include "common.hpp"
 #include "wave_dpp.hpp"
 
@@ -133,11 +134,7 @@ __device__ __forceinline__ void cloud_sort_body(int n, const float *__restrict__
   const int c0 = tid * kPer;
   int sum = 0;
   for (int i = 0; i < kPer; ++i) sum += lh[c0 + i];
-  int incl = sum;
-  for (int m = 1; m < 64; m <<= 1) {
-    const int o = __shfl_up(incl, m);
-    if ((tid & 63) >= m) incl += o;
-  }
+  const int incl = sn::wave_inclusive_scan(sum);
   __shared__ int wsum[16];
   if ((tid & 63) == 63) wsum[tid >> 6] = incl;
   __syncthreads();

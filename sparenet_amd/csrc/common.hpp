@@ -165,6 +165,12 @@ __device__ __forceinline__ float ordered_float(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
+// the part of row b of a ragged batch that is points: lengths[b] held to [0, n]; all n rows where lengths is null
+__device__ __forceinline__ int clamped_length(const int *lengths, int b, int n) {
+  const int len = lengths ? lengths[b] : n;
+  return len < 0 ? 0 : (len > n ? n : len);
+}
+
 // A workspace is described ONCE, by a layout function that takes its arrays from a Carver in order and returns the
 // struct of pointers.  On the caller's base pointer that carves the workspace; on a null base it only measures
 // (every pointer comes back null), which is what the sn_*_workspace_bytes exports and the "workspace too small" checks

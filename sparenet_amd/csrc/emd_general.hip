@@ -21,6 +21,7 @@
 // fp64-detour value only where the target can enter its top two, and the group merges its partial results with the
 // (thread(k), k) tie key.  The top-2 VALUES do not depend on the partition, and tie_key restores the reference's
 // index rule, so G is a pure performance choice.
+#include "block_scan.hpp"
 #include "common.hpp"
 #include "emd_bid.hpp"
 
@@ -351,31 +352,17 @@ constexpr int kSortThreads = 1024;
 
 // one workgroup per cloud: off = exclusive scan of count over the cloud's targets; run = 0
 __global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scan_kernel(int m, BwdWs w) {
-  __shared__ int s_wave[kSortThreads / 64];
-  __shared__ int s_carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ alignas(16) sn::BlockScan<kSortThreads> scan;
   const size_t o = (size_t)blockIdx.x * m;
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
+  scan.reset(0);
   for (int k0 = 0; k0 < m; k0 += kSortThreads) {
-    const int k = k0 + tid;
-    const int v = k < m ? w.count[o + k] : 0;
-    int incl = v;  // inclusive scan inside the wave
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = s_carry;
-    for (int q = 0; q < wave; ++q) before += s_wave[q];
-    if (k < m) {
-      w.off[o + k] = before + incl - v;
-      w.run[o + k] = 0;
-    }
-    __syncthreads();
-    if (tid == kSortThreads - 1) s_carry = before + incl;
-    __syncthreads();
+    const int k = k0 + threadIdx.x;
+    scan.chunk(k < m ? w.count[o + k] : 0, [&](int start) {
+      if (k < m) {
+        w.off[o + k] = start;
+        w.run[o + k] = 0;
+      }
+    });
   }
 }
 

@@ -138,11 +138,7 @@ __device__ __forceinline__ Pick block_pick(const Best &best, Slot *slots, int pa
   }
 }
 
-// the part of a cloud's row that is points, and where the sampling starts: device values are held to their ranges
-__device__ __forceinline__ int cloud_length(const int *lengths, int b, int n) {
-  const int len = lengths ? lengths[b] : n;
-  return len < 0 ? 0 : (len > n ? n : len);
-}
+// where the sampling starts in a cloud of len points (sn::clamped_length): the device value is held to its range
 __device__ __forceinline__ int cloud_start(const int *start, int b, int len) {
   const int s = start ? start[b] : 0;
   return s < 0 ? 0 : (s >= len ? len - 1 : s);
@@ -162,7 +158,7 @@ __global__ __launch_bounds__(T) void fps_resident_kernel(int n, int m, const flo
                                                          float *__restrict__ min_dist) {
   __shared__ Slot slots[2 * (T / 64)];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int len = cloud_length(lengths, b, n);
+  const int len = sn::clamped_length(lengths, b, n);
   idx += (size_t)b * m;
   if (min_dist) min_dist += (size_t)b * m;
   if (len == 0) return empty_row(m, idx, min_dist);
@@ -203,7 +199,7 @@ __global__ __launch_bounds__(kWsThreads) void fps_workspace_kernel(int n, int m,
                                                                    float *__restrict__ mind) {
   __shared__ Slot slots[2 * (kWsThreads / 64)];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int len = cloud_length(lengths, b, n);
+  const int len = sn::clamped_length(lengths, b, n);
   idx += (size_t)b * m;
   if (min_dist) min_dist += (size_t)b * m;
   if (len == 0) return empty_row(m, idx, min_dist);

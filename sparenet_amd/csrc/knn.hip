@@ -14,6 +14,7 @@
 //   * sn_graph_feature_forward / backward: out[b, c, n, j] = x[b, c, idx[b,n,j]] - x[b, c, n],
 //     out[b, C + c, n, j] = x[b, c, n]  (the cat((feature - x, x)).permute(0,3,1,2) of :899-905).
 #include "common.hpp"
+#include "index_lists.hpp"
 
 namespace {
 
@@ -103,55 +104,8 @@ __global__ __launch_bounds__(256) void graph_feature_fwd_kernel(const float *__r
 }
 
 // Backward without floating-point atomics: the graph is the same for all channels, so the edges
-// are first inverted once (for every point q the list of edges (p, j) with idx[p, j] == q: count,
-// scan, fill), then one thread per (b, ch, q) adds its own terms and the terms of its incoming edges.
-__global__ __launch_bounds__(256) void graph_count_kernel(const long long *__restrict__ idx, int n,
-                                                          int k, long edges, int *__restrict__ cnt) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < edges; e += (long)gridDim.x * blockDim.x) {
-    const long b = e / ((long)n * k);
-    atomicAdd(&cnt[b * n + idx[e]], 1);
-  }
-}
-
-// per cloud: in-place exclusive scan of the n counts
-__global__ __launch_bounds__(1024) void graph_scan_kernel(int *__restrict__ cnt, int n) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int tid = threadIdx.x;
-  int *c = cnt + (size_t)blockIdx.x * n;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + tid;
-    const int v = i < n ? c[i] : 0;
-    int incl = v;
-    for (int m = 1; m < 64; m <<= 1) {
-      const int u = __shfl_up(incl, m);
-      if ((tid & 63) >= m) incl += u;
-    }
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int w = 0; w < (tid >> 6); ++w) pre += wsum[w];
-    if (i < n) c[i] = pre + incl - v;
-    __syncthreads();
-    if (tid == 1023) carry = pre + incl;
-    __syncthreads();
-  }
-}
-
-// elist[b][start(q) ...] = edge ids p * k + j; afterwards offs[b][q] is the END of q's list
-__global__ __launch_bounds__(256) void graph_fill_kernel(const long long *__restrict__ idx, int n, int k,
-                                                         long edges, int *__restrict__ offs,
-                                                         int *__restrict__ elist) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < edges; e += (long)gridDim.x * blockDim.x) {
-    const long b = e / ((long)n * k);
-    const int local = (int)(e - b * n * k);
-    const int pos = atomicAdd(&offs[b * n + idx[e]], 1);
-    elist[b * (long)n * k + pos] = local;
-  }
-}
-
+// are first inverted once (index_lists.hpp: for every point q the list of edges p * k + j with idx[p, j] == q),
+// then one thread per (b, ch, q) adds its own terms and the terms of its incoming edges.
 __global__ __launch_bounds__(256) void graph_feature_bwd_kernel(const float *__restrict__ g,
                                                                 const int *__restrict__ offs,
                                                                 const int *__restrict__ elist, int c,
@@ -211,22 +165,9 @@ extern "C" int sn_graph_feature_forward(const float *x, const long long *idx, in
   return sn::launch_status("sn_graph_feature_forward");
 }
 
-namespace {
-
-// the backward's workspace
-struct EdgeWs {
-  int *offs;   // [b, n] edges arriving at each point, then their starts
-  int *elist;  // [b, n, k] the edges grouped by the point they arrive at
-};
-EdgeWs edge_layout(sn::Carver &c, int b, int n, int k) {
-  return {c.take256<int>((size_t)b * n * 4), c.take<int>((size_t)b * n * k * 4)};
-}
-
-}  // namespace
-
 extern "C" size_t sn_graph_feature_backward_workspace_bytes(int b, int n, int k) {
   if (b < 1 || n < 1 || k < 1) return 0;
-  return sn::layout_bytes(edge_layout, b, n, k);
+  return sn::layout_bytes(index_lists_layout, b, n, (long)n * k);
 }
 
 extern "C" int sn_graph_feature_backward(const float *grad_out, const long long *idx, int b, int c,
@@ -235,16 +176,12 @@ extern "C" int sn_graph_feature_backward(const float *grad_out, const long long 
   SN_REQUIRE(grad_out && idx && grad_x && workspace, "sn_graph_feature_backward: null pointer");
   SN_REQUIRE(b >= 1 && c >= 1 && n >= 1 && k >= 1, "sn_graph_feature_backward: bad sizes");
   sn::Carver carver(workspace);
-  const EdgeWs w = edge_layout(carver, b, n, k);
+  const IndexLists w = index_lists_layout(carver, b, n, (long)n * k);  // the edges grouped by the point they arrive at
   SN_REQUIRE(workspace_bytes >= carver.bytes(), "sn_graph_feature_backward: workspace too small");
   hipStream_t s = sn::as_stream(stream);
-  const long edges = (long)b * n * k;
-  SN_HIP(hipMemsetAsync(w.offs, 0, (size_t)b * n * 4, s));
-  graph_count_kernel<<<sn::grid_blocks(edges, kMaxBlocks), 256, 0, s>>>(idx, n, k, edges, w.offs);
-  graph_scan_kernel<<<b, 1024, 0, s>>>(w.offs, n);
-  graph_fill_kernel<<<sn::grid_blocks(edges, kMaxBlocks), 256, 0, s>>>(idx, n, k, edges, w.offs, w.elist);
+  if (const int rc = build_index_lists("sn_graph_feature_backward", idx, b, n, (long)n * k, w, s)) return rc;
   const long total = (long)b * c * n;
-  graph_feature_bwd_kernel<<<sn::grid_blocks(total, kMaxBlocks), 256, 0, s>>>(grad_out, w.offs, w.elist, c, n, k,
-                                                                               total, grad_x);
+  graph_feature_bwd_kernel<<<sn::grid_blocks(total, kMaxBlocks), 256, 0, s>>>(grad_out, w.offs, w.list, c, n, k,
+                                                                              total, grad_x);
   return sn::launch_status("sn_graph_feature_backward");
 }

@@ -18,10 +18,11 @@
 // segment's share at its offset: the concatenation in segment order, cut at nsample.
 // No workgroup waits for another, no atomics, no [b,m,n] intermediate.
 //
-// The backward inverts the slot lists once per call (count, scan, fill: integer atomics only, shared by all channels
-// and by grouping and interpolation), then one thread per (b, channel, target) adds its list.
+// The backward inverts the slot lists once per call (index_lists.hpp: integer atomics only, shared by all channels and
+// by grouping and interpolation), then one thread per (b, channel, target) adds its list.
 #include "chamfer_tile.hpp"
 #include "common.hpp"
+#include "index_lists.hpp"
 #include "../../include/ops/neighbors.h"
 
 namespace {
@@ -41,11 +42,6 @@ constexpr int kMaxBlocks = 65535;          // cap of the grid-stride launches
 constexpr int kMaxPoints = 1 << 30;
 
 static_assert(kWideTile % sn::ct::kChunk == 0 && kSplitTile % sn::ct::kChunk == 0 && sn::ct::kChunk == 8, "tile chunks");
-
-__device__ __forceinline__ int held_length(const int *lengths, int b, int n) {
-  const int len = lengths ? lengths[b] : n;
-  return len < 0 ? 0 : (len > n ? n : len);
-}
 
 struct SearchArgs {
   const float *xyz, *new_xyz;
@@ -71,9 +67,9 @@ __device__ __forceinline__ Place place_of(const SearchArgs &a) {
   p.lanes = blockDim.x / a.split;
   p.seg = threadIdx.x / p.lanes;
   p.gt = threadIdx.x - p.seg * p.lanes;
-  p.len = held_length(a.lengths, p.b, a.n);
+  p.len = sn::clamped_length(a.lengths, p.b, a.n);
   p.qi = (blockIdx.x - p.b * a.qblocks) * p.lanes + p.gt;
-  p.live = p.qi < held_length(a.new_lengths, p.b, a.m);
+  p.live = p.qi < sn::clamped_length(a.new_lengths, p.b, a.m);
   p.tile = a.split == 1 ? kWideTile : kSplitTile;
   const int seglen = sn::ceil_div(p.len, a.split);
   p.begin = p.seg * seglen < p.len ? p.seg * seglen : p.len;
@@ -293,54 +289,6 @@ __global__ __launch_bounds__(256) void interpolate_fwd_kernel(const float *__res
   }
 }
 
-// the backward's lists: for every target j of a cloud the slots (i, t) with idx[i, t] == j
-__global__ __launch_bounds__(256) void slot_count_kernel(const int *__restrict__ idx, int n, long slots, long total,
-                                                         int *__restrict__ offs) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const int j = idx[e];
-    if ((unsigned)j < (unsigned)n) atomicAdd(&offs[e / slots * n + j], 1);
-  }
-}
-
-// per cloud: in-place exclusive scan of the n counts
-__global__ __launch_bounds__(1024) void slot_scan_kernel(int *__restrict__ offs, int n) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int tid = threadIdx.x;
-  int *c = offs + (size_t)blockIdx.x * n;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + tid;
-    const int v = i < n ? c[i] : 0;
-    int incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d);
-      if ((tid & 63) >= d) incl += u;
-    }
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int w = 0; w < (tid >> 6); ++w) pre += wsum[w];
-    if (i < n) c[i] = pre + incl - v;
-    __syncthreads();
-    if (tid == 1023) carry = pre + incl;
-    __syncthreads();
-  }
-}
-
-// list[cloud][start(j) ...] = the slot's number i * s + t; afterwards offs[cloud][j] is the END of j's list
-__global__ __launch_bounds__(256) void slot_fill_kernel(const int *__restrict__ idx, int n, long slots, long total,
-                                                        int *__restrict__ offs, int *__restrict__ list) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const int j = idx[e];
-    if ((unsigned)j >= (unsigned)n) continue;
-    const long b = e / slots;
-    const int pos = atomicAdd(&offs[b * n + j], 1);
-    list[b * slots + pos] = (int)(e - b * slots);
-  }
-}
-
 // one thread per (cloud, channel, target): grad_out is [b,c,m,s] (weight null) or [b,c,m]
 __global__ __launch_bounds__(256) void group_bwd_kernel(const float *__restrict__ g, const float *__restrict__ weight,
                                                         const int *__restrict__ offs, const int *__restrict__ list,
@@ -361,14 +309,6 @@ __global__ __launch_bounds__(256) void group_bwd_kernel(const float *__restrict_
     }
     gf[e] = acc;
   }
-}
-
-struct SlotWs {
-  int *offs;   // [b, n] slots arriving at each target, then their starts, then their ends
-  int *list;   // [b, m * s] the slots grouped by the target they point at
-};
-SlotWs slot_layout(sn::Carver &c, int b, int n, int m, int s) {
-  return {c.take256<int>((size_t)b * n * 4), c.take<int>((size_t)b * m * s * 4)};
 }
 
 // ---------------------------------------------------------------------------------------------------- dispatch
@@ -500,7 +440,7 @@ extern "C" int sn_interpolate_forward(const float *features, const int *idx, con
 
 extern "C" size_t sn_group_backward_workspace_bytes(int b, int n, int m, int s) {
   if (b < 1 || n < 1 || m < 1 || s < 1) return 0;
-  return sn::layout_bytes(slot_layout, b, n, m, s);
+  return sn::layout_bytes(index_lists_layout, b, n, (long)m * s);
 }
 
 extern "C" int sn_group_backward(const float *grad_out, const int *idx, const float *weight, int b, int c, int n,
@@ -509,16 +449,13 @@ extern "C" int sn_group_backward(const float *grad_out, const int *idx, const fl
   SN_REQUIRE(grad_out && idx && grad_features && workspace, "sn_group_backward: null pointer");
   SN_REQUIRE(b >= 1 && c >= 1 && n >= 1 && m >= 1 && s >= 1, "sn_group_backward: need b,c,n,m,s >= 1");
   SN_REQUIRE(n <= kMaxPoints && (long)m * s <= kMaxPoints, "sn_group_backward: cloud too large");
+  const long slots = (long)m * s, total = (long)b * c * n;
   sn::Carver carver(workspace);
-  const SlotWs w = slot_layout(carver, b, n, m, s);
+  const IndexLists w = index_lists_layout(carver, b, n, slots);  // the slots grouped by the target they point at
   SN_REQUIRE(workspace && workspace_bytes >= carver.bytes(), "sn_group_backward: workspace too small (%zu < %zu)",
              workspace_bytes, carver.bytes());
   hipStream_t st = sn::as_stream(stream);
-  const long slots = (long)m * s, edges = (long)b * slots, total = (long)b * c * n;
-  SN_HIP(hipMemsetAsync(w.offs, 0, (size_t)b * n * 4, st));
-  slot_count_kernel<<<sn::grid_blocks(edges, kMaxBlocks), 256, 0, st>>>(idx, n, slots, edges, w.offs);
-  slot_scan_kernel<<<b, 1024, 0, st>>>(w.offs, n);
-  slot_fill_kernel<<<sn::grid_blocks(edges, kMaxBlocks), 256, 0, st>>>(idx, n, slots, edges, w.offs, w.list);
+  if (const int rc = build_index_lists("sn_group_backward", idx, b, n, slots, w, st)) return rc;
   group_bwd_kernel<<<sn::grid_blocks(total, kMaxBlocks), 256, 0, st>>>(grad_out, weight, w.offs, w.list, c, n, s,
                                                                        slots, total, grad_features);
   return sn::launch_status("sn_group_backward");

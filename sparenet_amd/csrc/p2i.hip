@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "block_scan.hpp"
 #include "common.hpp"
 #include "wave_dpp.hpp"
 
@@ -300,39 +301,25 @@ __global__ __launch_bounds__(1024) void p2i_bin_scan_kernel(const int *__restric
                                                             int *__restrict__ offs_out,
                                                             int cells_per_image,
                                                             const unsigned *__restrict__ need) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
+  __shared__ alignas(16) sn::BlockScan<1024> scan;
   if (*need == 0u) return;
   const int tid = threadIdx.x, b = blockIdx.x;
   int before = 0;
   for (long i = tid; i < (long)b * cells_per_image; i += 1024) before += counts[i];
   for (int m = 1; m < 64; m <<= 1) before += __shfl_xor(before, m);
-  if ((tid & 63) == 0) wsum[tid >> 6] = before;
+  if ((tid & 63) == 0) scan.wsum[tid >> 6] = before;  // idle until the first chunk
   __syncthreads();
-  if (tid == 0) {
-    int t = 0;
-    for (int w = 0; w < 16; ++w) t += wsum[w];
-    carry = t;
-  }
-  __syncthreads();
+  int t = 0;
+  if (tid == 0)
+    for (int w = 0; w < 16; ++w) t += scan.wsum[w];
+  scan.reset(t);
   const int *c = counts + (size_t)b * cells_per_image;
   int *o = offs_out + (size_t)b * cells_per_image;
   for (int base = 0; base < cells_per_image; base += 1024) {
     const int i = base + tid;
-    const int v = i < cells_per_image ? c[i] : 0;
-    int incl = v;
-    for (int m = 1; m < 64; m <<= 1) {
-      const int u = __shfl_up(incl, m);
-      if ((tid & 63) >= m) incl += u;
-    }
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int wv = 0; wv < (tid >> 6); ++wv) pre += wsum[wv];
-    if (i < cells_per_image) o[i] = pre + incl - v;
-    __syncthreads();
-    if (tid == 1023) carry = pre + incl;
-    __syncthreads();
+    scan.chunk(i < cells_per_image ? c[i] : 0, [&](int start) {
+      if (i < cells_per_image) o[i] = start;
+    });
   }
 }
 
@@ -376,8 +363,8 @@ __global__ __launch_bounds__(1024) void p2i_bin_grouped_kernel(
     unsigned *__restrict__ fmax_bits, unsigned *__restrict__ need, int ppi, int channels, int h, int w,
     int cells_x, int cells_y) {
   __shared__ int cnt[kGroupCells];
-  __shared__ int wsum[16];
-  __shared__ int carry, bad;
+  __shared__ alignas(16) sn::BlockScan<1024> scan;
+  __shared__ int bad;
   const int tid = threadIdx.x, b = blockIdx.x;
   const int cpi = cells_x * cells_y;
   const long base = (long)b * ppi;
@@ -398,24 +385,12 @@ __global__ __launch_bounds__(1024) void p2i_bin_grouped_kernel(
     return;
   }
   // exclusive scan of the counters -> first record of every cell (the image starts at b * ppi)
-  if (tid == 0) carry = (int)base;
-  __syncthreads();
+  scan.reset((int)base);
   for (int c0 = 0; c0 < cpi; c0 += 1024) {
     const int i = c0 + tid;
-    const int v = i < cpi ? cnt[i] : 0;
-    int incl = v;
-    for (int m = 1; m < 64; m <<= 1) {
-      const int u = __shfl_up(incl, m);
-      if ((tid & 63) >= m) incl += u;
-    }
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int wv = 0; wv < (tid >> 6); ++wv) pre += wsum[wv];
-    if (i < cpi) cnt[i] = pre + incl - v;
-    __syncthreads();
-    if (tid == 1023) carry = pre + incl;
-    __syncthreads();
+    scan.chunk(i < cpi ? cnt[i] : 0, [&](int start) {
+      if (i < cpi) cnt[i] = start;
+    });
   }
   float fm = 0.f;
   for (int i = tid; i < ppi; i += 1024) {

@@ -5,6 +5,7 @@
 // cuda/gridding/__init__.py:41-47).  The ragged ops take padding by position: the first lengths[b] rows of a cloud are
 // its points.  sn_pad_compact moves the rows that are points to the front, in their order, and says where each came
 // from; sn_pad_scatter_rows takes per-row values (gradients) back to the original places.
+#include "block_scan.hpp"
 #include "common.hpp"
 
 namespace {
@@ -12,7 +13,9 @@ namespace {
 constexpr int kScanThreads = 1024;
 
 // One workgroup per cloud, chunks of 1024 rows in ascending order with the running count carried in LDS: a stable
-// partition by one prefix scan, for any n, and no workgroup waits for another.
+// partition by one prefix scan, for any n, and no workgroup waits for another.  The chunk protocol is the one of
+// sn::BlockScan, written out: on sn::BlockScan this kernel measured 2 - 4 % slower (21.7 / 22.0 us against 21.3 / 20.9
+// at 32 x 16384 rows, same registers and LDS), and the cause was not found.
 __global__ __launch_bounds__(kScanThreads) void pad_compact_kernel(const float *__restrict__ xyz, int n,
                                                                    float *__restrict__ packed,
                                                                    int *__restrict__ lengths, int *__restrict__ src) {
@@ -33,11 +36,7 @@ __global__ __launch_bounds__(kScanThreads) void pad_compact_kernel(const float *
     }
     // the rule of sn_gridding_forward_padded, in its order; a NaN sum is not zero: the row is a point
     const int keep = i < n && !((x + y) + z == 0.f);
-    int incl = keep;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d);
-      if (lane >= d) incl += v;
-    }
+    const int incl = sn::wave_inclusive_scan(keep);
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     int before = s_carry;

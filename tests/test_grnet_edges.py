@@ -214,7 +214,7 @@ def test_edge_features_largest_case(dev):
     """Edge features forward + backward at b = 2, c = 3, n = 3000, k = 20: 360,000 elements.  Their launches are capped at
     65,535 blocks of 256 = 16.7 M elements; a case past that cap would need a 16.7 M-element edge tensor per channel pair
     and a [b, n, n] search to build it, far beyond a few seconds, so the grid-stride loops of graph_feature_fwd_kernel,
-    graph_count_kernel, graph_fill_kernel and graph_feature_bwd_kernel stay UNTESTED past their first pass."""
+    index_lists_count_kernel, index_lists_fill_kernel and graph_feature_bwd_kernel stay UNTESTED past their first pass."""
     from sparenet_amd.cuda.knn import get_graph_feature
 
     b, c, n, k = C.CAP_EDGE

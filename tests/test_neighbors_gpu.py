@@ -311,19 +311,11 @@ def _backward_idx(dev, case):
     return np.zeros((2, 256, 32), np.int32)          # all m * s = 8192 slots of a cloud on target 0
 
 
-@pytest.mark.parametrize("case", ["ball, pad first", "ball, pad none", "one target"])
-def test_backward_against_float64(dev, monkeypatch, case):
+def _check_backward(dev, idx, c, n, rng, what):
+    """grouping_operation and three_interpolate backward against float64; returns the list lengths [b, n]."""
     from sparenet_amd.cuda.neighbors import grouping_operation, three_interpolate
 
-    monkeypatch.delenv("SN_NEIGHBORS_SPLIT", raising=False)
-    idx = _backward_idx(dev, case)
-    if case == "ball, pad first":
-        assert (idx[:, :, -1] == idx[:, :, 0]).mean() > 0.5
-    elif case == "ball, pad none":
-        assert (idx == -1).mean() > 0.2
-    rng = np.random.default_rng(len(case))
-    b, c, n = 2, 5, 512
-    feats = rng.standard_normal((b, c, n)).astype(np.float32)
+    feats = rng.standard_normal((idx.shape[0], c, n)).astype(np.float32)
     w = _upstream(rng, idx.shape)
     for weight in (None, w):
         f = _t(feats, dev).requires_grad_(True)
@@ -337,13 +329,38 @@ def test_backward_against_float64(dev, monkeypatch, case):
         bound = sum_bound(length)[:, None, :] * mag
         err = np.abs(got - want)
         worst = np.unravel_index(np.argmax(err - bound), err.shape)
-        print(f"{case}, weight {weight is not None}: longest list {length.max()}, largest error / bound "
+        print(f"{what}, weight {weight is not None}: longest list {length.max()}, largest error / bound "
               f"{(err[bound > 0] / bound[bound > 0]).max():.3f}")
-        assert (err <= bound).all(), f"{case}: at {worst} error {err[worst]:.3e}, bound {bound[worst]:.3e}"
+        assert (err <= bound).all(), f"{what}: at {worst} error {err[worst]:.3e}, bound {bound[worst]:.3e}"
         empty = np.broadcast_to((length == 0)[:, None, :], got.shape)
         assert not got[empty].any()                      # targets without a slot are exactly 0
+        yield got, length
+
+
+@pytest.mark.parametrize("case", ["ball, pad first", "ball, pad none", "one target"])
+def test_backward_against_float64(dev, monkeypatch, case):
+    monkeypatch.delenv("SN_NEIGHBORS_SPLIT", raising=False)
+    idx = _backward_idx(dev, case)
+    if case == "ball, pad first":
+        assert (idx[:, :, -1] == idx[:, :, 0]).mean() > 0.5
+    elif case == "ball, pad none":
+        assert (idx == -1).mean() > 0.2
+    for got, length in _check_backward(dev, idx, 5, 512, np.random.default_rng(len(case)), case):
         if case == "one target":
             assert length[0, 0] == 8192 and not got[:, :, 1:].any()
+
+
+@pytest.mark.parametrize("n", [1024, 1025, 2049])
+def test_backward_lists_past_one_scan_chunk(dev, n):
+    """The inverted lists' scan hands a carry from one chunk of 1024 targets to the next: n at and just past one and two
+    chunks, a long list in the last chunk behind mostly empty ones."""
+    b, m, s = 2, 64, 8
+    rng = np.random.default_rng(n)
+    idx = rng.integers(0, n, (b, m, s)).astype(np.int32)
+    idx[rng.random(idx.shape) < 0.2] = -1
+    idx[:, :, 3] = n - 1
+    for got, length in _check_backward(dev, idx, 3, n, rng, f"n = {n}"):
+        assert (length[:, n - 1] >= m).all() and (length == 0).mean() > 0.5
 
 
 def test_interpolate_features_against_its_float64_composite(dev):

@@ -610,6 +610,28 @@ def test_hip_binning_grouped_layout_and_its_fallbacks_agree(dev):
 
 
 @pytest.mark.gpu
+def test_hip_binning_past_one_scan_chunk(dev):
+    """33 x 33 = 1089 cells per image: the scans of the cell counts (grouped kernel and generic kernels) hand a carry
+    from their first chunk of 1024 cells to the second, and the generic scan of image 1 starts behind image 0."""
+    from sparenet_amd.cuda.p2i_op import ext
+
+    g = torch.Generator().manual_seed(264)
+    B, n, S, R = 2, 1024, 264, 5.0
+    pts = torch.rand(B * n, 2, generator=g) * (S + 6) - 3
+    feat = torch.rand(B * n, 1, generator=g)
+    bi = torch.arange(B, dtype=torch.int32).repeat_interleave(n)
+    bg = torch.zeros(B, 1, S, S)
+    out0, ids0 = ext.p2i_max_forward_multi_gpu(pts.to(dev), feat.to(dev), bi.to(dev), bg.to(dev), 0, [R])
+    o, i = oracle.p2i_max_forward(pts.numpy(), feat.numpy(), bi.numpy(), bg.numpy(), R)
+    _close_maps(out0[0].cpu().numpy(), ids0[0].cpu().numpy(), o, i, "grouped", pts, feat, bg, R)
+    perm = torch.randperm(B * n, generator=g)       # the layout check fails on the device: the generic kernels
+    out1, ids1 = ext.p2i_max_forward_multi_gpu(pts[perm].to(dev), feat[perm].to(dev), bi[perm].to(dev), bg.to(dev), 0, [R])
+    assert torch.equal(out1, out0)
+    back = perm.to(dev)[ids1.clamp(min=0).long()]
+    assert torch.equal(torch.where(ids1 < 0, ids1.long(), back), ids0.long())
+
+
+@pytest.mark.gpu
 def test_hip_weight_series_error_bounds(dev):
     """The forward decides winners with an fp32 series of the cosine weight and only evaluates winners exactly;
     that is sound iff |series - exact| stays inside the band the kernel assumes (kWeightErr = 1.5e-6, of which
