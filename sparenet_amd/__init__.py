@@ -14,6 +14,19 @@ _REFERENCE_OP_PACKAGES = ("chamfer_distance", "chamfer_dist", "emd", "expansion_
                           "gridding", "gridding_loss", "cubic_feature_sampling")
 
 
+_SINKHORN_NAMES = ("sinkhorn_potentials", "sinkhorn_ot", "sinkhorn_divergence", "SinkhornDistance")
+
+
+def __getattr__(name):
+    """`sparenet_amd.sinkhorn_divergence` ...: the Sinkhorn transport loss (sparenet_amd.cuda.sinkhorn), imported at
+    its first use."""
+    if name in _SINKHORN_NAMES:
+        import importlib
+
+        return getattr(importlib.import_module("sparenet_amd.cuda.sinkhorn"), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 WAIT_POLICIES = ("fail", "recover", "nowait")   # SN_WAIT_FAIL / SN_WAIT_RECOVER / SN_WAIT_NOWAIT (sparenet_hip.h)
 
 
