@@ -15,6 +15,7 @@ _REFERENCE_OP_PACKAGES = ("chamfer_distance", "chamfer_dist", "emd", "expansion_
 
 
 _SINKHORN_NAMES = ("sinkhorn_potentials", "sinkhorn_ot", "sinkhorn_divergence", "SinkhornDistance")
+_SWD_NAMES = ("sliced_wasserstein", "sorted_projections", "random_directions", "SlicedWassersteinDistance")
 
 
 def __getattr__(name):
@@ -24,6 +25,10 @@ def __getattr__(name):
         import importlib
 
         return getattr(importlib.import_module("sparenet_amd.cuda.sinkhorn"), name)
+    if name in _SWD_NAMES:      # the sliced Wasserstein distance (sparenet_amd.cuda.swd), the same way
+        import importlib
+
+        return getattr(importlib.import_module("sparenet_amd.cuda.swd"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

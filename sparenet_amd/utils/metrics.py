@@ -92,6 +92,16 @@ def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pr
     return out
 
 
+def swd(pred, gt, n_slices=128, p=2, directions=None, generator=None, pred_lengths=None, gt_lengths=None):
+    """Sliced Wasserstein distance of pred [B,N,3] and gt [B,M,3] per sample [B] (sparenet_amd.cuda.swd): for p = 2 the
+    root of the mean squared 1-D transport cost over the slices -- a distance in the clouds' units -- for p = 1 the mean
+    cost itself."""
+    from sparenet_amd.cuda.swd import sliced_wasserstein
+
+    value = sliced_wasserstein(pred, gt, n_slices, p, directions, generator, pred_lengths, gt_lengths)
+    return torch.sqrt(value) if p == 2 else value
+
+
 def fpd(pred, gt, model, batch_size=100):
     """Frechet Point-cloud Distance of the SETS pred [N,n,3] and gt [M,m,3] (one scalar, float64) with `model`, a loaded
     sparenet_amd.Frechet.pointnet.PointNetCls(k=16): calculate_fpd on the clouds' own device (the fused PointNet
