@@ -16,6 +16,7 @@ _REFERENCE_OP_PACKAGES = ("chamfer_distance", "chamfer_dist", "emd", "expansion_
 
 _SINKHORN_NAMES = ("sinkhorn_potentials", "sinkhorn_ot", "sinkhorn_divergence", "SinkhornDistance")
 _SWD_NAMES = ("sliced_wasserstein", "sorted_projections", "random_directions", "SlicedWassersteinDistance")
+_DCD_NAMES = ("density_aware_chamfer", "dcd_from_search", "DensityAwareChamferDistance")
 
 
 def __getattr__(name):
@@ -29,6 +30,10 @@ def __getattr__(name):
         import importlib
 
         return getattr(importlib.import_module("sparenet_amd.cuda.swd"), name)
+    if name in _DCD_NAMES:      # the density-aware Chamfer distance (sparenet_amd.cuda.dcd)
+        import importlib
+
+        return getattr(importlib.import_module("sparenet_amd.cuda.dcd"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

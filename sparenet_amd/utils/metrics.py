@@ -30,7 +30,7 @@ def f_score_from_chamfer(dist1, dist2, th=0.01):
 
 
 def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, with_emd=True, emd_any_size=False,
-                             pred_lengths=None, gt_lengths=None):
+                             pred_lengths=None, gt_lengths=None, with_dcd=False, dcd_alpha=1000.0, dcd_n_lambda=1.0):
     """pred [B,N,3], gt [B,M,3] on the GPU -> dict of per-sample tensors [B]:
     'F-Score', 'ChamferDistance' (x1000, mean dist1 + mean dist2, utils/misc.py:198-201 with
     ChamferDistanceMean) and 'EMD' (x100; needs N == M, a multiple of 1024).
@@ -43,10 +43,18 @@ def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, wit
     rows rounded once to fp32, where the dense path takes torch's fp32 mean: the two agree to fp32 rounding, not bit
     for bit.
     'EMD' then needs emd_any_size=True and pred_lengths[i] <= gt_lengths[i] for every cloud (pred bids; checked when
-    the lengths are host values)."""
+    the lengths are host values).
+    with_dcd=True adds 'DCD', the density-aware Chamfer distance (sparenet_amd.cuda.dcd) with dcd_alpha and
+    dcd_n_lambda, from the SAME search: there is no second one, the other keys keep their bits, and -- the call being
+    the distance op's own -- only 'DCD' carries a gradient then."""
     if pred_lengths is not None or gt_lengths is not None:
-        return _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths)
-    dist1, dist2 = ChamferDistanceFunction.apply(pred, gt)
+        return _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths,
+                               with_dcd, dcd_alpha, dcd_n_lambda)
+    if with_dcd:
+        value, raw = _dcd_with_search(pred, gt, dcd_alpha, dcd_n_lambda)
+        dist1, dist2 = raw["dist1"], raw["dist2"]
+    else:
+        dist1, dist2 = ChamferDistanceFunction.apply(pred, gt)
     out = {"F-Score": f_score_from_chamfer(dist1, dist2, th),
            "ChamferDistance": (dist1.mean(dim=1) + dist2.mean(dim=1)) * 1000}
     if with_emd and emd_any_size:
@@ -56,10 +64,20 @@ def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, wit
     elif with_emd:
         dist, _ = emdModule()(pred, gt, emd_eps, emd_iters)
         out["EMD"] = torch.sqrt(dist).mean(dim=1) * 100
+    if with_dcd:
+        out["DCD"] = value
     return out
 
 
-def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths):
+def _dcd_with_search(pred, gt, alpha, n_lambda, pred_lengths=None, gt_lengths=None):
+    """(DCD [B], the raw outputs of its one Chamfer search)."""
+    from sparenet_amd.cuda.dcd import density_aware_chamfer
+
+    return density_aware_chamfer(pred, gt, alpha, n_lambda, "none", pred_lengths, gt_lengths, return_raw=True)
+
+
+def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths,
+                    with_dcd=False, dcd_alpha=1000.0, dcd_n_lambda=1.0):
     from sparenet_amd.cuda.ragged import chamfer_ragged, device_lengths, emd_ragged, masked_mean, valid_mask
 
     b = pred.size(0)
@@ -78,7 +96,11 @@ def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pr
             if bad:
                 raise ValueError(f"fused_validation_metrics: 'EMD' needs pred_lengths[i] <= gt_lengths[i] (pred bids for "
                                  f"gt); cloud {bad[0]} has {hp[bad[0]]} > {hg[bad[0]]}")
-    dist1, dist2 = chamfer_ragged(pred, gt, l1, l2)
+    if with_dcd:
+        value, raw = _dcd_with_search(pred, gt, dcd_alpha, dcd_n_lambda, l1, l2)
+        dist1, dist2 = raw["dist1"], raw["dist2"]
+    else:
+        dist1, dist2 = chamfer_ragged(pred, gt, l1, l2)
     th2 = float(th) * float(th)
     m1, m2 = valid_mask(l1, pred.size(1), pred.device), valid_mask(l2, gt.size(1), gt.device)
     precision = ((dist1 < th2) & m1).sum(dim=1).double() / l1.clamp(1, pred.size(1))
@@ -89,6 +111,8 @@ def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pr
     if with_emd:
         dist, _ = emd_ragged(pred, gt, l1, l2, emd_eps, emd_iters)
         out["EMD"] = masked_mean(torch.sqrt(dist), l1) * 100
+    if with_dcd:
+        out["DCD"] = value
     return out
 
 
@@ -100,6 +124,15 @@ def swd(pred, gt, n_slices=128, p=2, directions=None, generator=None, pred_lengt
 
     value = sliced_wasserstein(pred, gt, n_slices, p, directions, generator, pred_lengths, gt_lengths)
     return torch.sqrt(value) if p == 2 else value
+
+
+def dcd(pred, gt, alpha=1000.0, n_lambda=1.0, ratio="none", pred_lengths=None, gt_lengths=None):
+    """Density-aware Chamfer distance of pred [B,N,3] and gt [B,M,3] per sample [B] (in [0, 1] with ratio="none")
+    (sparenet_amd.cuda.dcd): the exponential Chamfer terms, each divided by the number of points that share its
+    neighbour to the power n_lambda (0, 0.5 or 1)."""
+    from sparenet_amd.cuda.dcd import density_aware_chamfer
+
+    return density_aware_chamfer(pred, gt, alpha, n_lambda, ratio, pred_lengths, gt_lengths)
 
 
 def fpd(pred, gt, model, batch_size=100):
