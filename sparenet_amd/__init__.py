@@ -17,6 +17,7 @@ _REFERENCE_OP_PACKAGES = ("chamfer_distance", "chamfer_dist", "emd", "expansion_
 _SINKHORN_NAMES = ("sinkhorn_potentials", "sinkhorn_ot", "sinkhorn_divergence", "SinkhornDistance")
 _SWD_NAMES = ("sliced_wasserstein", "sorted_projections", "random_directions", "SlicedWassersteinDistance")
 _DCD_NAMES = ("density_aware_chamfer", "dcd_from_search", "DensityAwareChamferDistance")
+_NORMALS_NAMES = ("local_pca", "surface_variation", "estimate_normals", "normal_consistency", "point_to_plane_chamfer")
 
 
 def __getattr__(name):
@@ -34,6 +35,10 @@ def __getattr__(name):
         import importlib
 
         return getattr(importlib.import_module("sparenet_amd.cuda.dcd"), name)
+    if name in _NORMALS_NAMES:      # normals, local frames and the metrics on them (sparenet_amd.cuda.normals)
+        import importlib
+
+        return getattr(importlib.import_module("sparenet_amd.cuda.normals"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

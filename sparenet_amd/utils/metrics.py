@@ -30,7 +30,8 @@ def f_score_from_chamfer(dist1, dist2, th=0.01):
 
 
 def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, with_emd=True, emd_any_size=False,
-                             pred_lengths=None, gt_lengths=None, with_dcd=False, dcd_alpha=1000.0, dcd_n_lambda=1.0):
+                             pred_lengths=None, gt_lengths=None, with_dcd=False, dcd_alpha=1000.0, dcd_n_lambda=1.0,
+                             with_normals=False, normals_k=16):
     """pred [B,N,3], gt [B,M,3] on the GPU -> dict of per-sample tensors [B]:
     'F-Score', 'ChamferDistance' (x1000, mean dist1 + mean dist2, utils/misc.py:198-201 with
     ChamferDistanceMean) and 'EMD' (x100; needs N == M, a multiple of 1024).
@@ -46,13 +47,19 @@ def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, wit
     the lengths are host values).
     with_dcd=True adds 'DCD', the density-aware Chamfer distance (sparenet_amd.cuda.dcd) with dcd_alpha and
     dcd_n_lambda, from the SAME search: there is no second one, the other keys keep their bits, and -- the call being
-    the distance op's own -- only 'DCD' carries a gradient then."""
+    the distance op's own -- only 'DCD' carries a gradient then.
+    with_normals=True adds 'NormalConsistency' (sparenet_amd.cuda.normals.normal_consistency, normals estimated from
+    normals_k neighbours) from the SAME search as well: the other keys keep their bits; the search is then called
+    without autograd, so 'ChamferDistance' carries no gradient."""
     if pred_lengths is not None or gt_lengths is not None:
         return _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths,
-                               with_dcd, dcd_alpha, dcd_n_lambda)
+                               with_dcd, dcd_alpha, dcd_n_lambda, with_normals, normals_k)
     if with_dcd:
         value, raw = _dcd_with_search(pred, gt, dcd_alpha, dcd_n_lambda)
         dist1, dist2 = raw["dist1"], raw["dist2"]
+        found = (raw["idx1"], raw["idx2"])
+    elif with_normals:
+        dist1, dist2, *found = _plain_search(pred, gt)[:4]
     else:
         dist1, dist2 = ChamferDistanceFunction.apply(pred, gt)
     out = {"F-Score": f_score_from_chamfer(dist1, dist2, th),
@@ -66,7 +73,25 @@ def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, wit
         out["EMD"] = torch.sqrt(dist).mean(dim=1) * 100
     if with_dcd:
         out["DCD"] = value
+    if with_normals:
+        out["NormalConsistency"] = _consistency_from_search(pred, gt, found, normals_k)
     return out
+
+
+def _plain_search(pred, gt, pred_lengths=None, gt_lengths=None):
+    """(dist1, dist2, idx1, idx2, ...) of the one Chamfer search, without autograd: the distances' bits are those of
+    the differentiable call."""
+    from sparenet_amd.cuda.dcd import _check_pair, _search
+
+    _check_pair("fused_validation_metrics", pred, gt)
+    return _search(pred.detach(), gt.detach(), pred_lengths, gt_lengths)
+
+
+def _consistency_from_search(pred, gt, found, k, pred_lengths=None, gt_lengths=None):
+    from sparenet_amd.cuda.normals import estimate_normals, normal_consistency_from_search
+
+    return normal_consistency_from_search(found[0], found[1], estimate_normals(pred.detach(), k, pred_lengths),
+                                          estimate_normals(gt.detach(), k, gt_lengths), pred_lengths, gt_lengths)
 
 
 def _dcd_with_search(pred, gt, alpha, n_lambda, pred_lengths=None, gt_lengths=None):
@@ -77,7 +102,7 @@ def _dcd_with_search(pred, gt, alpha, n_lambda, pred_lengths=None, gt_lengths=No
 
 
 def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pred_lengths, gt_lengths,
-                    with_dcd=False, dcd_alpha=1000.0, dcd_n_lambda=1.0):
+                    with_dcd=False, dcd_alpha=1000.0, dcd_n_lambda=1.0, with_normals=False, normals_k=16):
     from sparenet_amd.cuda.ragged import chamfer_ragged, device_lengths, emd_ragged, masked_mean, valid_mask
 
     b = pred.size(0)
@@ -99,6 +124,9 @@ def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pr
     if with_dcd:
         value, raw = _dcd_with_search(pred, gt, dcd_alpha, dcd_n_lambda, l1, l2)
         dist1, dist2 = raw["dist1"], raw["dist2"]
+        found = (raw["idx1"], raw["idx2"])
+    elif with_normals:
+        dist1, dist2, *found = _plain_search(pred, gt, l1, l2)[:4]
     else:
         dist1, dist2 = chamfer_ragged(pred, gt, l1, l2)
     th2 = float(th) * float(th)
@@ -113,6 +141,8 @@ def _ragged_metrics(pred, gt, th, emd_eps, emd_iters, with_emd, emd_any_size, pr
         out["EMD"] = masked_mean(torch.sqrt(dist), l1) * 100
     if with_dcd:
         out["DCD"] = value
+    if with_normals:
+        out["NormalConsistency"] = _consistency_from_search(pred, gt, found, normals_k, l1, l2)
     return out
 
 
@@ -133,6 +163,15 @@ def dcd(pred, gt, alpha=1000.0, n_lambda=1.0, ratio="none", pred_lengths=None, g
     from sparenet_amd.cuda.dcd import density_aware_chamfer
 
     return density_aware_chamfer(pred, gt, alpha, n_lambda, ratio, pred_lengths, gt_lengths)
+
+
+def normal_consistency(pred, gt, k=16, pred_lengths=None, gt_lengths=None, pred_normals=None, gt_normals=None):
+    """Normal consistency of pred [B,N,3] and gt [B,M,3] per sample [B], in [0, 1] (sparenet_amd.cuda.normals): the mean
+    |cosine| between each point's normal and the normal of its nearest neighbour in the other cloud, both ways.  Normals
+    that are not given are estimated from k neighbours."""
+    from sparenet_amd.cuda.normals import normal_consistency as consistency
+
+    return consistency(pred, gt, pred_normals, gt_normals, k, pred_lengths, gt_lengths)
 
 
 def fpd(pred, gt, model, batch_size=100):
