@@ -26,6 +26,7 @@
 #include "cloud_sort.hpp"
 #include "common.hpp"
 #include "wave_dpp.hpp"
+#include "../../include/ops/mds_plan.h"
 #include "../../include/sn_expf.h"
 
 // Round 5's two attempts at the surface regime's round -- several picks per round (exact, 3.3 picks per round, 19.0 ms
@@ -1055,12 +1056,157 @@ float *generic_layout(sn::Carver &c, int b, int n) { return c.take<float>((size_
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------
+// The dispatch (include/ops/mds_plan.h): which kernels one call launches, from values alone.  sn_mds reads the knobs,
+// the device and the wait policy and launches from this answer; sn_mds_workspace_bytes and sn_mds_plan ask it too.
+// The instance tables (register slots per lane -> compiled instance) exist here and nowhere else;
+// tests/test_mds_plan.py sweeps the invariants the kernels rely on and pins which instance each GPU case reaches.
+// ---------------------------------------------------------------------------------------
+namespace {
+
+struct MdsPlan {
+  int family = SN_MDS_FAMILY_REGISTERS;
+  int instance = 0, zlds = 0, static_bs = 0;  // mds_kernel<instance, zlds, static_bs> / mds_clustered_kernel<instance>
+  int threads = 1, lg = 0, ppt = 1;           // lanes of the one-workgroup launch, their log2, points per lane
+  size_t lds = 0, lds_opt_in = 0;             // its dynamic LDS, and the limit it opts in to (0: none)
+  int team_g = 1, team_slots = 0, team_pg = 0, team_nw = 0, team_instance = 0;
+  size_t team_lds = 0, team_lds_opt_in = 0, team_ctl_bytes = 0;
+  bool team_every_regime = false;
+  size_t workspace_bytes = 0;
+};
+
+// cus: compute units (0: no teams); gmax: cap on the team size; ratio_given: SN_MDS_RATIO is set; solo: one workgroup
+// per cloud whatever the device (wait policy, graph capture)
+int mds_plan(int b, int n, int cus, int gmax, bool ratio_given, bool solo, MdsPlan *out) {
+  MdsPlan pl;
+  int bs = 1, lg = 0;
+  while (bs * 2 <= n && bs < 1024) {
+    bs *= 2;
+    ++lg;
+  }
+  const int ppt = (n + bs - 1) / bs;
+  pl.threads = bs;
+  pl.lg = lg;
+  pl.ppt = ppt;
+  if (mds_use_clustered(n)) {
+    pl.family = SN_MDS_FAMILY_CLUSTERED;
+    pl.workspace_bytes = sn::layout_bytes(clustered_layout, b, n);
+    // Dense-regime clouds go to a team of G workgroups each (mds_dense_team_kernel); the one-workgroup kernel behind it
+    // then skips them.  SN_MDS_G caps G (1: off).
+    // Measured at n = 19384 -> 16384 (profiles/r03_*_mds_teams.txt): a team round costs ~1.9 us (G = 8) / 1.7 us
+    // (G = 16) whatever the regime, the one-workgroup kernel 1.1 us (surface) ... 4.3 us (cut ball = the cloud);
+    // the two cross where the cut ball's squared radius is ~0.15 of the box diagonal's.
+    // A member owns PG x nw consecutive groups of 64 sorted points (nw <= 16 waves, PG register slots per lane): the
+    // cloud's ceil(n / 64) groups are dealt out evenly.  (Rounds 3-5 dealt out whole slots of 1024 points: at n = 19384
+    // and G = 16 ten members held two slots each and six held nothing.)  G = the largest power of two <= 32 such that
+    // every cloud's team fits one XCD's share of the compute units -- so the whole grid is resident: the members wait
+    // for each other -- and a member still has four waves of points.
+    const int groups = (n + 63) / 64;
+    int team_g = 1, team_slots = 0;
+    if (cus >= 64 && cus % 8 == 0 && ppt >= 2) {
+      const int per = cus / 8, tpx = (b + 7) / 8;
+      int g = 1;
+      while (g * 2 * tpx <= per && g * 2 <= gmax && g * 2 * 4 <= groups) g *= 2;
+      team_g = g;
+      team_slots = 8 * tpx;
+    }
+    if (solo) team_g = 1;  // no teams under nowait, once the device's latch is set, or under graph capture
+    if (team_g >= 2) {
+      const int per_member = (groups + team_g - 1) / team_g;  // groups of 64 points a member owns
+      const int pg = (per_member + 15) / 16;                  // register slots per lane
+      const int nw = (per_member + pg - 1) / pg;              // waves per member (<= 16)
+      SN_REQUIRE(team_slots * team_g <= 1024 && pg <= 10, "sn_mds: unexpected team geometry");
+      // the compiled instances; a member of instance P owns P x nw groups, so the last members of a rounded-up team
+      // own fewer points or none
+      const int p = pg <= 6 ? pg : pg <= 8 ? 8 : 10;
+      pl.team_g = team_g;
+      pl.team_slots = team_slots;
+      pl.team_pg = pg;
+      pl.team_nw = nw;
+      pl.team_instance = p;
+      pl.team_lds = (size_t)p * nw * 64 * 8;
+      pl.team_lds_opt_in = 160 * 1024 - 4096;
+      pl.team_ctl_bytes = 128 + 128 * 3 * (size_t)team_slots * team_g;
+      // Round 6: with several picks per exchange a team of >= 8 members beats the one-workgroup kernel in EVERY regime
+      // of a SpareNet-sized cloud -- surface regime (mml 0.0085, 19384 -> 16384) 17.7 -> 10.6 ms at <= 8 clouds, 17.9
+      // -> 15.4 at 32; surface-like clouds 18.0-23.5 -> 10.6-12.2 (profiles/r06_h_mds_team_everywhere.txt) -- so such
+      // clouds all go to teams; smaller clouds and teams keep the measured cross-over (SN_MDS_RATIO).
+      pl.team_every_regime = team_g >= 8 && n >= 8192 && !ratio_given;
+    }
+    // exact slot counts near the register limit (19 at SpareNet's n = 19384): every unused
+    // slot costs three VGPRs and the 1024-lane workgroup only has 128 per lane
+    pl.instance = ppt <= 2 ? 2 : ppt <= 4 ? 4 : ppt <= 8 ? 8 : ppt <= 12 ? 12 : ppt <= 16 ? 16 : ppt <= 18 ? ppt : 19;
+    // the kernel initialises all `instance` y/z slots of every lane, padding included, so the launch carries that many
+    pl.lds = (size_t)pl.instance * 1024 * 8;
+    pl.lds_opt_in = 160 * 1024 - 1024;
+  } else if (bs < 1024) {
+    // What mds_use_clustered leaves to the one-workgroup kernel: n < 2048 (ppt <= 2) and n > 19456 (ppt >= 20) -- up to
+    // 20352 with y and z in LDS, up to 24576 with z in LDS, beyond that the generic kernel.
+    pl.instance = 2;
+  } else if (ppt <= 2) {
+    pl.instance = 2;
+    pl.static_bs = 1024;
+  } else if (ppt <= 20 && (size_t)n * 8 + 1024 <= 160 * 1024) {
+    // y,z of 20480 points = 160 KiB minus the hand-off slots: opt in to the large LDS carve
+    pl.instance = 20;
+    pl.zlds = 2;
+    pl.static_bs = 1024;
+    pl.lds = (size_t)n * 4 * 2;
+    pl.lds_opt_in = 160 * 1024 - 512;
+  } else if (ppt <= 24) {
+    pl.instance = 24;
+    pl.zlds = 1;
+    pl.static_bs = 1024;
+    pl.lds = (size_t)n * 4;
+    pl.lds_opt_in = 100 * 1024;
+  } else {
+    pl.family = SN_MDS_FAMILY_GENERIC;
+    pl.workspace_bytes = sn::layout_bytes(generic_layout, b, n);
+  }
+  *out = pl;
+  return 0;
+}
+
+}  // namespace
+
 extern "C" size_t sn_mds_workspace_bytes(int b, int n) {
   if (b < 1 || n < 1) return 0;
-  if (mds_use_clustered(n)) return sn::layout_bytes(clustered_layout, b, n);
-  int bs = 1;
-  while (bs * 2 <= n && bs < 1024) bs *= 2;
-  return (n + bs - 1) / bs <= 24 ? 0 : sn::layout_bytes(generic_layout, b, n);
+  MdsPlan pl;  // the workspace depends on the family alone, not on the device
+  return mds_plan(b, n, 0, 1, false, true, &pl) == 0 ? pl.workspace_bytes : 0;
+}
+
+extern "C" int sn_mds_plan(int b, int n, int cus, int g_cap, int ratio_given, int solo, int *plan, int plan_words) {
+  SN_REQUIRE(plan, "sn_mds_plan: null pointer");
+  SN_REQUIRE(plan_words >= SN_MDS_PLAN_WORDS, "sn_mds_plan: plan needs %d words (got %d)", SN_MDS_PLAN_WORDS, plan_words);
+  SN_REQUIRE(b >= 1 && n >= 1, "sn_mds_plan: need b,n >= 1 (got %d,%d)", b, n);
+  SN_REQUIRE(n < (1 << 22), "sn_mds_plan: cloud too large");
+  if (cus <= 0) {
+    int dev = 0;
+    SN_HIP(hipGetDevice(&dev));
+    SN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  MdsPlan pl;
+  if (const int rc = mds_plan(b, n, cus, g_cap >= 1 && g_cap <= 32 ? g_cap : 32, ratio_given != 0, solo != 0, &pl)) return rc;
+  plan[SN_MDS_PLAN_FAMILY] = pl.family;
+  plan[SN_MDS_PLAN_INSTANCE] = pl.instance;
+  plan[SN_MDS_PLAN_ZLDS] = pl.zlds;
+  plan[SN_MDS_PLAN_STATIC_BS] = pl.static_bs;
+  plan[SN_MDS_PLAN_THREADS] = pl.threads;
+  plan[SN_MDS_PLAN_PPT] = pl.ppt;
+  plan[SN_MDS_PLAN_LDS_BYTES] = (int)pl.lds;
+  plan[SN_MDS_PLAN_LDS_OPT_IN] = (int)pl.lds_opt_in;
+  plan[SN_MDS_PLAN_TEAM_G] = pl.team_g;
+  plan[SN_MDS_PLAN_TEAM_SLOTS] = pl.team_slots;
+  plan[SN_MDS_PLAN_TEAM_PG] = pl.team_pg;
+  plan[SN_MDS_PLAN_TEAM_NW] = pl.team_nw;
+  plan[SN_MDS_PLAN_TEAM_INSTANCE] = pl.team_instance;
+  plan[SN_MDS_PLAN_TEAM_LDS_BYTES] = (int)pl.team_lds;
+  plan[SN_MDS_PLAN_TEAM_LDS_OPT_IN] = (int)pl.team_lds_opt_in;
+  plan[SN_MDS_PLAN_TEAM_EVERY_REGIME] = pl.team_every_regime ? 1 : 0;
+  plan[SN_MDS_PLAN_TEAM_CTL_BYTES] = (int)pl.team_ctl_bytes;
+  plan[SN_MDS_PLAN_WORKSPACE_LO] = (int)(unsigned)(pl.workspace_bytes & 0xffffffffu);
+  plan[SN_MDS_PLAN_WORKSPACE_HI] = (int)(pl.workspace_bytes >> 32);
+  return 0;
 }
 
 extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_mst_length,
@@ -1069,29 +1215,19 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
   SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "sn_mds: need b,n,m >= 1 (got %d,%d,%d)", b, n, m);
   SN_REQUIRE(m <= n, "sn_mds: npoint (%d) must not exceed the cloud size (%d)", m, n);
   SN_REQUIRE(n < (1 << 22), "sn_mds: cloud too large");
-  int bs = 1, lg = 0;
-  while (bs * 2 <= n && bs < 1024) {
-    bs *= 2;
-    ++lg;
-  }
-  const int ppt = (n + bs - 1) / bs;
+  // the family and the workspace do not depend on the device: planned first without one, and only a clustered call
+  // asks the runtime (below) and plans again with what it learned
+  MdsPlan pl;
+  if (const int rc = mds_plan(b, n, 0, 1, false, true, &pl)) return rc;
   hipStream_t s = sn::as_stream(stream);
   if (sn::prof_enabled()) sn::prof_begin("mds", s);
-  if (mds_use_clustered(n)) {
+  if (pl.family == SN_MDS_FAMILY_CLUSTERED) {
     sn::Carver carver(workspace);
     const MdsClusteredWs w = clustered_layout(carver, b, n);
     SN_REQUIRE(workspace && workspace_bytes >= carver.bytes(), "sn_mds: workspace too small (%zu < %zu)",
                workspace_bytes, carver.bytes());
     SN_REQUIRE(cloud_sort(b, n, xyz, w.bbox, w.hist, w.cell_of, w.perm, s) == 0,
                "sn_mds: cannot size the sort kernel's LDS");
-    // Dense-regime clouds go to a team of G workgroups each (mds_dense_team_kernel); the one-workgroup kernel below
-    // then skips them.  G = the largest power of two <= 16 such that every cloud's team fits one XCD's share of the
-    // compute units and the whole grid is resident (the members wait for each other); SN_MDS_G overrides (1: off).
-    // Measured at n = 19384 -> 16384 (profiles/r03_*_mds_teams.txt): a team round costs ~1.9 us (G = 8) / 1.7 us
-    // (G = 16) whatever the regime, the one-workgroup kernel 1.1 us (surface) ... 4.3 us (cut ball = the cloud);
-    // the two cross where the cut ball's squared radius is ~0.15 of the box diagonal's.
-    int team_g = 1, team_slots = 0;
-    float team_ratio_eff = 0.f;   // = team_ratio, or ~0 where teams serve every regime (set below)
     // a cloud goes to a team when its cut ball's squared radius exceeds this fraction of the squared diagonal of
     // its bounding box (SN_MDS_RATIO; measured cross-over)
     // (0.12 in rounds 3-4, from uniform cubes at chosen mean MST lengths.  The first sampler call of an UNTRAINED generator
@@ -1103,120 +1239,83 @@ extern "C" int sn_mds(const float *xyz, int b, int n, int m, const float *mean_m
     const char *ratio_env = SN_KNOB("SN_MDS_RATIO");
     const float ratio_v = ratio_env ? (float)atof(ratio_env) : 0.075f;
     const float team_ratio = ratio_v > 0.f ? ratio_v : 0.075f;
-    team_ratio_eff = team_ratio;
     int recover = 0;
     unsigned *recovered = nullptr;
-    {
-      int dev = 0, cus = 0;
-      SN_HIP(hipGetDevice(&dev));
-      if (const int rc = sn::check_sticky(dev, "sn_mds")) return rc;
-      SN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-      const char *g_env = SN_KNOB("SN_MDS_G");
-      const int gmax = g_env && atoi(g_env) >= 1 && atoi(g_env) <= 32 ? atoi(g_env) : 32;
-      // wait policy (sparenet_hip.h): no teams under nowait or once the device's latch is set
-      const int policy = sn::wait_policy();
-      const bool solo = sn::wait_solo(dev);
-      // A member owns PG x nw consecutive groups of 64 sorted points (nw <= 16 waves, PG register slots per lane): the
-      // cloud's ceil(n / 64) groups are dealt out evenly.  (Rounds 3-5 dealt out whole slots of 1024 points: at n = 19384
-      // and G = 16 ten members held two slots each and six held nothing.)  G = the largest power of two <= 32 such that
-      // every cloud's team fits one XCD's share of the compute units and a member still has four waves of points.
-      const int groups = (n + 63) / 64;
-      if (cus >= 64 && cus % 8 == 0 && ppt >= 2) {
-        const int per = cus / 8, tpx = (b + 7) / 8;
-        int g = 1;
-        while (g * 2 * tpx <= per && g * 2 <= gmax && g * 2 * 4 <= groups) g *= 2;
-        team_g = g;
-        team_slots = 8 * tpx;
+    int dev = 0, cus = 0;
+    SN_HIP(hipGetDevice(&dev));
+    if (const int rc = sn::check_sticky(dev, "sn_mds")) return rc;
+    SN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const char *g_env = SN_KNOB("SN_MDS_G");
+    const int gmax = g_env && atoi(g_env) >= 1 && atoi(g_env) <= 32 ? atoi(g_env) : 32;
+    // wait policy (sparenet_hip.h): no teams under nowait or once the device's latch is set
+    const int policy = sn::wait_policy();
+    const bool solo = sn::wait_solo(dev) || sn::capturing(s);  // under graph capture: the one-workgroup kernel only
+    if (const int rc = mds_plan(b, n, cus, gmax, ratio_env != nullptr, solo, &pl)) return rc;
+    // ~0 where teams serve every regime
+    const float team_ratio_eff = pl.team_every_regime ? 1e-30f : team_ratio;
+    if (pl.team_g >= 2) {
+      const int team_g = pl.team_g, team_slots = pl.team_slots, nw = pl.team_nw;
+      unsigned *sticky = policy == SN_WAIT_FAIL ? sn::sticky_device_word(dev) : nullptr;
+      if (policy == SN_WAIT_RECOVER) {
+        recover = 1;
+        recovered = sn::recovered_device_word(dev, sn::kRecoveredMds);
       }
-      if (team_g >= 2 && sn::capturing(s)) team_g = 1;  // under graph capture: the one-workgroup kernel only
-      if (solo) team_g = 1;
-      // Round 6: with several picks per exchange a team of >= 8 members beats the one-workgroup kernel in EVERY regime of
-      // a SpareNet-sized cloud -- surface regime (mml 0.0085, 19384 -> 16384) 17.7 -> 10.6 ms at <= 8 clouds, 17.9 ->
-      // 15.4 at 32; surface-like clouds 18.0-23.5 -> 10.6-12.2 (profiles/r06_h_mds_team_everywhere.txt) -- so such
-      // clouds all go to teams; smaller clouds and teams keep the measured cross-over above.
-      if (team_g >= 8 && n >= 8192 && !ratio_env) team_ratio_eff = 1e-30f;
-      if (team_g >= 2) {
-        const int per_member = (groups + team_g - 1) / team_g;        // groups of 64 points a member owns
-        const int pg = (per_member + 15) / 16;                        // register slots per lane
-        const int nw = (per_member + pg - 1) / pg;                    // waves per member (<= 16)
-        unsigned *sticky = policy == SN_WAIT_FAIL ? sn::sticky_device_word(dev) : nullptr;
-        if (policy == SN_WAIT_RECOVER) {
-          recover = 1;
-          recovered = sn::recovered_device_word(dev, sn::kRecoveredMds);
-        }
-        // SN_MDS_DIAG=8 (tests): the second member of cloud 0's team leaves at once and the polls give up early
-        const char *dg = SN_KNOB("SN_MDS_DIAG");
-        const bool park = dg && atoi(dg) == 8;
-        SN_REQUIRE(team_slots * team_g <= 1024 && pg <= 10, "sn_mds: unexpected team geometry");
-        SN_HIP(hipMemsetAsync(w.tctl, 0, 128 + 128 * 3 * (size_t)team_slots * team_g, s));
-        sn::PersistentLaunch chain(dev, s);  // never beside another team-waiting launch of this process (common.hpp)
+      // SN_MDS_DIAG=8 (tests): the second member of cloud 0's team leaves at once and the polls give up early
+      const char *dg = SN_KNOB("SN_MDS_DIAG");
+      const bool park = dg && atoi(dg) == 8;
+      SN_HIP(hipMemsetAsync(w.tctl, 0, pl.team_ctl_bytes, s));
+      sn::PersistentLaunch chain(dev, s);  // never beside another team-waiting launch of this process (common.hpp)
 #define SN_MDST(P)                                                                                          \
-  {                                                                                                         \
+  case P: {                                                                                                 \
     SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_dense_team_kernel<P>),                   \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));             \
-    mds_dense_team_kernel<P><<<team_slots * team_g, nw * 64, (size_t)P * nw * 64 * 8, s>>>(                 \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.team_lds_opt_in));       \
+    mds_dense_team_kernel<P><<<team_slots * team_g, nw * 64, pl.team_lds, s>>>(                             \
         b, n, m, xyz, w.perm, w.bbox, mean_mst_length, idx, w.tctl, sticky, team_g, team_slots,             \
         park ? 3 : 1, park ? 1u << 14 : 1u << 24, team_ratio_eff, nw);                                      \
-  }
-        if (pg <= 1) SN_MDST(1)
-        else if (pg <= 2) SN_MDST(2)
-        else if (pg <= 3) SN_MDST(3)
-        else if (pg <= 4) SN_MDST(4)
-        else if (pg <= 5) SN_MDST(5)
-        else if (pg <= 6) SN_MDST(6)
-        else if (pg <= 8) SN_MDST(8)
-        else SN_MDST(10)
-#undef SN_MDST
+  } break;
+      switch (pl.team_instance) {
+        SN_MDST(1) SN_MDST(2) SN_MDST(3) SN_MDST(4) SN_MDST(5) SN_MDST(6) SN_MDST(8) SN_MDST(10)
+        default: SN_REQUIRE(false, "sn_mds: no team kernel for %d register slots", pl.team_instance);
       }
+#undef SN_MDST
     }
-    const float skip_ratio = team_g >= 2 ? team_ratio_eff : 0.f;
-    const size_t lds = (size_t)ppt * 1024 * 8;
+    const float skip_ratio = pl.team_g >= 2 ? team_ratio_eff : 0.f;
 #define SN_MDSC(P)                                                                               \
-  {                                                                                              \
+  case P: {                                                                                      \
     /* every call: the attribute belongs to the CURRENT device (several devices per process under    \
        DataParallel), it is not a per-process fact */                                            \
     SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_clustered_kernel<P>),         \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));  \
-    mds_clustered_kernel<P><<<b, 1024, lds, s>>>(n, m, xyz, w.perm, w.bbox, mean_mst_length, idx, \
-                                                 skip_ratio, recover, recovered);                \
-  }
-    // exact slot counts near the register limit (19 at SpareNet's n = 19384): every unused
-    // slot costs three VGPRs and the 1024-lane workgroup only has 128 per lane
-    if (ppt <= 2) SN_MDSC(2)
-    else if (ppt <= 4) SN_MDSC(4)
-    else if (ppt <= 8) SN_MDSC(8)
-    else if (ppt <= 12) SN_MDSC(12)
-    else if (ppt <= 16) SN_MDSC(16)
-    else if (ppt == 17) SN_MDSC(17)
-    else if (ppt == 18) SN_MDSC(18)
-    else SN_MDSC(19)
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_opt_in)); \
+    mds_clustered_kernel<P><<<b, 1024, pl.lds, s>>>(n, m, xyz, w.perm, w.bbox, mean_mst_length, idx, \
+                                                    skip_ratio, recover, recovered);             \
+  } break;
+    switch (pl.instance) {
+      SN_MDSC(2) SN_MDSC(4) SN_MDSC(8) SN_MDSC(12) SN_MDSC(16) SN_MDSC(17) SN_MDSC(18) SN_MDSC(19)
+      default: SN_REQUIRE(false, "sn_mds: no clustered kernel for %d slots", pl.instance);
+    }
 #undef SN_MDSC
     if (sn::prof_enabled()) sn::prof_end("mds", s);
     return sn::launch_status("sn_mds");
   }
-  // What mds_use_clustered leaves to the one-workgroup kernel: n < 2048 (ppt <= 2) and n > 19456 (ppt >= 20) -- up to
-  // 20352 with y and z in LDS, up to 24576 with z in LDS, beyond that the generic kernel.
-#define SN_MDS_Z(P, C) \
-  mds_kernel<P, C, 1024><<<b, 1024, (size_t)n * 4 * C, s>>>(n, m, xyz, mean_mst_length, idx, lg)
-  if (bs < 1024) mds_kernel<2, 0, 0><<<b, bs, 0, s>>>(n, m, xyz, mean_mst_length, idx, lg);
-  else if (ppt <= 2) SN_MDS_Z(2, 0);
-  else if (ppt <= 20 && (size_t)n * 8 + 1024 <= 160 * 1024) {
-    // y,z of 20480 points = 160 KiB minus the hand-off slots: opt in to the large LDS carve
-    SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_kernel<20, 2, 1024>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-    SN_MDS_Z(20, 2);
-  } else if (ppt <= 24) {
-    SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_kernel<24, 1, 1024>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    SN_MDS_Z(24, 1);
-  }
-  else {
+  const int bs = pl.threads, lg = pl.lg;
+  if (pl.family == SN_MDS_FAMILY_GENERIC) {
     sn::Carver carver(workspace);
     float *dens = generic_layout(carver, b, n);
     SN_REQUIRE(workspace && workspace_bytes >= carver.bytes(), "sn_mds: workspace too small for n=%d", n);
     mds_kernel_generic<<<b, bs, 0, s>>>(n, m, xyz, mean_mst_length, dens, idx, lg);
+  } else if (pl.static_bs == 0) {
+    mds_kernel<2, 0, 0><<<b, bs, 0, s>>>(n, m, xyz, mean_mst_length, idx, lg);
+  } else if (pl.instance == 2) {
+    mds_kernel<2, 0, 1024><<<b, 1024, pl.lds, s>>>(n, m, xyz, mean_mst_length, idx, lg);
+  } else if (pl.instance == 20) {
+    SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_kernel<20, 2, 1024>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_opt_in));
+    mds_kernel<20, 2, 1024><<<b, 1024, pl.lds, s>>>(n, m, xyz, mean_mst_length, idx, lg);
+  } else {
+    SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mds_kernel<24, 1, 1024>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_opt_in));
+    mds_kernel<24, 1, 1024><<<b, 1024, pl.lds, s>>>(n, m, xyz, mean_mst_length, idx, lg);
   }
-#undef SN_MDS_Z
   if (sn::prof_enabled()) sn::prof_end("mds", s);
   return sn::launch_status("sn_mds");
 }

@@ -4,7 +4,10 @@ CPU: oracle (libm expf, bs=1) vs golden index sequences from the reference kerne
 race-free single-thread instantiation (tests/golden/gen_emulated.py mds); the cross-
 thread tie rule vs a direct simulation of the reference's reduction tree
 (MDS_cuda.cu:81-87, :139-198); sn_expf vs libm.
-GPU: HIP vs oracle (sn_expf, reference thread count): index sequences exact.
+GPU: HIP vs oracle (sn_expf, reference thread count): index sequences exact.  Which kernel
+instance a shape runs is asked of sn_mds_plan, never claimed in a comment: tests/mds_plan_cases.py
+holds one case per compiled instance and switch-over, tests/test_mds_plan.py pins that table on
+the CPU, and test_hip_every_instance_matches_oracle runs it here.
 """
 import glob
 import os
@@ -13,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import mds_plan_cases as mc
 import oracle
 
 
@@ -126,14 +130,46 @@ def _hip_mds(x, m, mml, dev):
     return minimum_density_sample(torch.from_numpy(x).to(dev), m, torch.from_numpy(mml).to(dev)).cpu().numpy()
 
 
+def _reached(b, n):
+    """(family, instance, ZLDS, compile-time workgroup size, team size, team instance, teams take every regime) of a
+    call with default knobs on 256 compute units."""
+    p = mc.plan(b, n)
+    return (p["family"], p["instance"], p["zlds"], p["static_bs"], p["team_g"], p["team_instance"],
+            p["team_every_regime"])
+
+
+def test_what_the_older_gpu_shapes_reach_on_256_compute_units():
+    """The shapes of the GPU tests below name no kernel; this is what the dispatch makes of them -- stated here so that
+    a retuning shows up as a diff of this table instead of a comment going stale."""
+    R, G, C = mc.REGISTERS, mc.GENERIC, mc.CLUSTERED
+    for (b, n), want in {
+            # test_hip_matches_oracle
+            (2, 300): (R, 2, 0, 0, 1, 0, 0), (3, 64): (R, 2, 0, 0, 1, 0, 0), (1, 17): (R, 2, 0, 0, 1, 0, 0),
+            (1, 1): (R, 2, 0, 0, 1, 0, 0), (2, 1024): (R, 2, 0, 1024, 1, 0, 0),
+            (1, 22000): (R, 24, 1, 1024, 1, 0, 0), (1, 30000): (G, 0, 0, 0, 1, 0, 0),
+            # every cloud on team<1> of 32, whatever its regime: the clustered kernel behind it returns at its first test
+            (1, 9000): (C, 12, 0, 0, 32, 1, 1), (1, 19384): (C, 19, 0, 0, 32, 1, 1),
+            # team<1> for clouds above the cross-over only; the all-zero densities at 2048 and the clouds at 5000
+            # are below it and sampled by clustered<2> / clustered<8>
+            (1, 2048): (C, 2, 0, 0, 8, 1, 0), (2, 5000): (C, 8, 0, 0, 16, 1, 0),
+            # test_hip_full_size_sparenet_shape, test_hip_dense_regime_teams_and_mixed_batches
+            (4, 19384): (C, 19, 0, 0, 32, 1, 1), (5, 19384): (C, 19, 0, 0, 32, 1, 1),
+            (12, 6000): (C, 8, 0, 0, 16, 1, 0), (33, 4096): (C, 4, 0, 0, 4, 1, 0), (70, 2048): (C, 2, 0, 0, 2, 1, 0),
+            # test_hip_team_multi_pick_corner_cases
+            (4, 2048): (C, 2, 0, 0, 8, 1, 0), (2, 8192): (C, 8, 0, 0, 32, 1, 1), (3, 19384): (C, 19, 0, 0, 32, 1, 1),
+            (8, 19384): (C, 19, 0, 0, 32, 1, 1), (9, 19384): (C, 19, 0, 0, 16, 2, 1), (1, 8192): (C, 8, 0, 0, 32, 1, 1),
+    }.items():
+        assert _reached(b, n) == want, (b, n)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("b,n,m,mml", [
     (2, 300, 128, 0.05), (1, 9000, 600, 0.012), (3, 64, 64, 0.2), (2, 1024, 512, 0.03),
     (1, 2048, 300, 1e-4),      # all-zero densities: pure tie-rule order, bs = 1024
     (2, 5000, 1000, 0.02), (1, 19384, 1500, 0.008), (1, 17, 9, 0.1), (1, 1, 1, 0.1),
-    (1, 22000, 400, 0.01),     # 22 points per lane: z-in-LDS variant
-    (1, 30000, 300, 0.01),     # generic fallback with the state in global memory
-])
+    (1, 22000, 400, 0.01),     # 22 points per lane
+    (1, 30000, 300, 0.01),     # 30 points per lane
+])                             # (the kernels these reach: test_what_the_older_gpu_shapes_reach_on_256_compute_units)
 def test_hip_matches_oracle(b, n, m, mml, dev):
     rng = np.random.default_rng(n + m)
     x = rng.random((b, n, 3), dtype=np.float32)
@@ -201,8 +237,8 @@ def test_hip_full_length_on_surface_clouds(kind, mml, dev):
                                    (70, 2048, 1500)])
 def test_hip_dense_regime_teams_and_mixed_batches(b, n, m, dev):
     """Clouds whose cut ball covers a good part of their bounding box are sampled by a TEAM of workgroups
-    (mds_dense_team_kernel: 16 / 8 / 4 / 2 workgroups per cloud depending on the batch, candidates exchanged through
-    stamped 64-bit words), the others by the one-workgroup kernel -- in ONE call when a batch mixes both.  The batch
+    (mds_dense_team_kernel: 32 / 32 / 16 / 4 / 2 workgroups per cloud for these batches on 256 compute units, pinned by
+    test_what_the_older_gpu_shapes_reach_on_256_compute_units; candidates exchanged through stamped 64-bit words), the others by the one-workgroup kernel -- in ONE call when a batch mixes both.  The batch
     here alternates mean MST lengths on both sides of the cross-over; every row must equal the oracle's sequence."""
     rng = np.random.default_rng(b * 1000 + n)
     x = rng.random((b, n, 3), dtype=np.float32)
@@ -242,3 +278,46 @@ def test_hip_team_multi_pick_corner_cases(b, n, m, mml, kind, dev):
     assert np.array_equal(got, want)
     if m == n:
         assert all(len(set(r.tolist())) == n for r in got)
+
+
+# ------------------------------------------------------------------ every compiled instance, by the plan
+_case_refs = {}
+
+
+def _case_inputs(c):
+    """(xyz, mean MST lengths, oracle rows) of a case, computed once."""
+    if c.id not in _case_refs:
+        x, mm = mc.clouds(c)
+        want = oracle.mds(x, c.m, mm, exp_mode=1)
+        want.setflags(write=False)
+        _case_refs[c.id] = (x, mm, want)
+    return _case_refs[c.id]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", mc.CASES, ids=lambda c: c.id)
+def test_hip_every_instance_matches_oracle(c, dev, monkeypatch):
+    """One case per compiled sampler instance, team geometry and switch-over (tests/mds_plan_cases.py): a dense cube and
+    a sphere in the surface regime per call, 600-1500 picks so that the slot summaries and the absorption culling are in
+    play.  The case first asks sn_mds_plan, with the device's own compute-unit count, for the kernels its call will
+    launch and asserts the instance it was written for; then every row must equal the oracle's, twice."""
+    for knob in ("SN_MDS_G", "SN_MDS_RATIO"):
+        monkeypatch.delenv(knob, raising=False)
+    for knob, value in c.env.items():
+        monkeypatch.setenv(knob, value)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    with torch.cuda.device(dev):
+        p = mc.case_plan(c, cus=0)            # <= 0: the current device's compute units
+    assert p == mc.case_plan(c, cus=cus)
+    got_plan = {k: p[k] for k in c.expect}
+    if cus != mc.CUS and got_plan != c.expect:
+        pytest.skip(f"written for {mc.CUS} compute units; with {cus} this call runs {got_plan}, not {c.expect}")
+    assert got_plan == c.expect
+    x, mm, want = _case_inputs(c)
+    # the surface cloud must exercise the arithmetic: when every increment underflows the row is the tie rule's order
+    assert c.b == 1 or not np.array_equal(want[1], mc.tie_rule_row(c.n, c.m))
+    assert all(len(set(r.tolist())) == c.m for r in want)
+    got = _hip_mds(x, c.m, mm, dev)
+    for i in range(c.b):
+        assert np.array_equal(got[i], want[i]), f"cloud {i}: first difference at pick {int(np.argmax(got[i] != want[i]))}"
+    assert np.array_equal(_hip_mds(x, c.m, mm, dev), got)       # run to run
