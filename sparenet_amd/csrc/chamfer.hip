@@ -25,6 +25,7 @@
 #include "block_scan.hpp"
 #include "chamfer_tile.hpp"
 #include "common.hpp"
+#include "sorted_lists.hpp"
 
 namespace {
 
@@ -41,12 +42,8 @@ using sn::ct::kTileF4;
 constexpr int kQPL = 4;                  // queries per lane
 constexpr int kQPB = kThreads * kQPL;    // queries per block
 
-// a cloud's point count from lengths[b], held to [0, width] so that no value a caller uploads can address outside the
-// cloud's rows
-__device__ __forceinline__ int ragged_len(const int *__restrict__ lengths, int b, int width) {
-  const int v = lengths[b];
-  return v < 0 ? 0 : (v > width ? width : v);
-}
+// a cloud's point count is sn::clamped_length: lengths[b] held to [0, width], so that no value a caller uploads can
+// address outside the cloud's rows
 __device__ __forceinline__ const int *pick_lengths(int second, const int *l1, const int *l2) { return second ? l2 : l1; }
 
 // Len is empty for dense batches (sn_chamfer_forward: the instantiation has the kernel arguments and the code it
@@ -78,8 +75,11 @@ __global__ __launch_bounds__(kThreads) void chamfer_fwd_kernel(
   const int wt = dir ? N : M;   // targets: row stride
   int nq = wq, nt = wt;         // ... and how many of the rows are points
   if constexpr (kRagged) {      // two wave-uniform loads per workgroup
-    nq = ragged_len(pick_lengths(dir, len...), b, wq);
-    nt = ragged_len(pick_lengths(dir ^ 1, len...), b, wt);
+    // loaded first: the entry point has checked the pointers, and on a loaded value clamped_length's null test folds
+    const int vq = pick_lengths(dir, len...)[b];
+    nq = sn::clamped_length(&vq, 0, wq);
+    const int vt = pick_lengths(dir ^ 1, len...)[b];
+    nt = sn::clamped_length(&vt, 0, wt);
   }
   const float *__restrict__ q = (dir ? xyz2 : xyz1) + (size_t)b * wq * 3;
   const float *__restrict__ t = (dir ? xyz1 : xyz2) + (size_t)b * wt * 3;
@@ -224,9 +224,7 @@ __global__ __launch_bounds__(kThreads) void chamfer_fwd_kernel(
 // the lists out of bounds, so they are clamped (the forward never produces one)
 __device__ __forceinline__ int clamp_idx(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
-constexpr int kLongList = 64;      // inverse lists longer than this are sorted and summed by a workgroup
-constexpr int kLongSortCap = 16384;  // ... in LDS up to this length (64 KB); longer ones by one thread, in place
-
+// the sort of a list, kLongList, kLongSortCap and the rule for the lists beyond them: sorted_lists.hpp
 struct BwdLists {
   int *cnt;    // [B, N + M]  how many points of the other cloud chose me (entries 0..N-1: cloud 1, then cloud 2)
   int *off;    // [B, N + M]  list start
@@ -257,11 +255,27 @@ template <bool kRagged>
 __device__ __forceinline__ CloudLen cloud_len(const int *__restrict__ len1, const int *__restrict__ len2, int b, int N,
                                               int M) {
   if constexpr (kRagged) {
-    const int n1 = ragged_len(len1, b, N), n2 = ragged_len(len2, b, M);
+    // the entry point has checked len1 and len2; on a kernel argument the compiler keeps clamped_length's null test
+    // all the same, on a loaded value it folds it away
+    const int v1 = len1[b], v2 = len2[b];
+    const int n1 = sn::clamped_length(&v1, 0, N), n2 = sn::clamped_length(&v2, 0, M);
     return (n1 > 0 && n2 > 0) ? CloudLen{n1, n2} : CloudLen{0, 0};
   } else {
     return CloudLen{N, M};
   }
+}
+
+// The element-wise kernels number the rows of the batch e = 0 .. B (N + M) - 1: the B N rows of cloud 1, then the B M of
+// cloud 2.  They write `second` (a row of cloud 2) and f (its number among the rows of its side) out themselves, as
+// `e >= total1` and `second ? e - total1 : e`: the compiler specialises f inside a kernel's branches on `second` only
+// when it meets that select in the kernel, and a helper that hands f back costs instructions in the loop.
+struct Row {
+  int b, self;  // the row's cloud, its number inside the cloud: f = b * (second ? M : N) + self
+};
+__device__ __forceinline__ Row row_of(bool second, long f, int N, int M) {
+  const int na = second ? M : N;
+  const int b = (int)(f / na);
+  return {b, (int)(f - (long)b * na)};
 }
 
 template <bool kRagged>
@@ -275,10 +289,10 @@ __global__ __launch_bounds__(256) void chamfer_bwd_count_kernel(const int *__res
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const bool second = e >= total1;
     const long f = second ? e - total1 : e;
-    const int b = (int)(f / (second ? M : N));
+    const auto [b, self] = row_of(second, f, N, M);
     const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
     if constexpr (kRagged) {
-      if ((int)(f - (long)b * (second ? M : N)) >= (second ? L.n2 : L.n1)) continue;
+      if (self >= (second ? L.n2 : L.n1)) continue;
     }
     // a cloud-1 query j votes for cloud-2 point idx1[j] (slot N + idx1[j]); a cloud-2 query for slot idx2[k]
     const int slot = second ? clamp_idx(idx2[f], L.n1) : N + clamp_idx(idx1[f], L.n2);
@@ -301,7 +315,7 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_scan_kernel(int NM, const in
       if (i < NM) {
         off[o + i] = start;
         fill[o + i] = start;
-        if (c > kLongList) longs[1 + atomicAdd(&longs[0], 1)] = (int)(o + i);
+        if (c > kLongList) register_long_list(longs, (int)(o + i));
       }
     });
   }
@@ -319,9 +333,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_fill_kernel(const int *__rest
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const bool second = e >= total1;
     const long f = second ? e - total1 : e;
-    const int na = second ? M : N;
-    const int b = (int)(f / na);
-    const int self = (int)(f - (long)b * na);
+    const auto [b, self] = row_of(second, f, N, M);
     const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
     if constexpr (kRagged) {
       if (self >= (second ? L.n2 : L.n1)) continue;
@@ -365,7 +377,7 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_lists_kernel(const int *__re
         cnt[o + i] = c;
         off[o + i] = start;
         lc[i] = start;
-        if (c > kLongList) longs[1 + atomicAdd(&longs[0], 1)] = (int)(o + i);
+        if (c > kLongList) register_long_list(longs, (int)(o + i));
       }
     });
   }
@@ -374,43 +386,6 @@ __global__ __launch_bounds__(1024) void chamfer_bwd_lists_kernel(const int *__re
     const bool second = e >= N;
     const int pos = atomicAdd(&lc[second ? clamp_idx(i2[e - N], L.n1) : N + clamp_idx(i1[e], L.n2)], 1);
     list[o + pos] = second ? e - N : e;
-  }
-}
-
-// in-place ascending sort of a short int array in global memory owned by the calling thread
-__device__ __forceinline__ void sort_ints(int *a, int n) {
-  if (n <= 16) {  // insertion sort
-    for (int i = 1; i < n; ++i) {
-      const int v = a[i];
-      int j = i - 1;
-      while (j >= 0 && a[j] > v) {
-        a[j + 1] = a[j];
-        --j;
-      }
-      a[j + 1] = v;
-    }
-    return;
-  }
-  // heap sort: O(n log n) also for the degenerate case of thousands of queries sharing one neighbour
-  auto sift = [&](int start, int end) {
-    int root = start;
-    for (;;) {
-      int child = 2 * root + 1;
-      if (child > end) break;
-      if (child + 1 <= end && a[child] < a[child + 1]) ++child;
-      if (a[root] >= a[child]) break;
-      const int t = a[root];
-      a[root] = a[child];
-      a[child] = t;
-      root = child;
-    }
-  };
-  for (int start = (n - 2) / 2; start >= 0; --start) sift(start, n - 1);
-  for (int end = n - 1; end > 0; --end) {
-    const int t = a[0];
-    a[0] = a[end];
-    a[end] = t;
-    sift(0, end - 1);
   }
 }
 
@@ -427,9 +402,8 @@ __global__ __launch_bounds__(256) void chamfer_bwd_gather_kernel(
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const bool second = e >= total1;
     const long f = second ? e - total1 : e;
-    const int na = second ? M : N, nb = second ? N : M;
-    const int b = (int)(f / na);
-    const int self = (int)(f - (long)b * na);
+    const int nb = second ? N : M;
+    const auto [b, self] = row_of(second, f, N, M);
     const float *a = second ? xyz2 : xyz1;   // my cloud
     const float *o = second ? xyz1 : xyz2;   // the other cloud
     const float *gda = second ? gd2 : gd1, *gdo = second ? gd1 : gd2;
@@ -489,6 +463,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_long_kernel(
   const int nlong = longs[0];
   for (int li = blockIdx.x; li < nlong; li += gridDim.x) {
     const long gslot = longs[1 + li];
+    // a list is registered by its slot, where a cloud's two sides follow each other -- not by row_of's element number
     const int b = (int)(gslot / NM), sl = (int)(gslot - (long)b * NM);
     const bool second = sl >= N;
     const int self = second ? sl - N : sl;
@@ -499,32 +474,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_long_kernel(
     const float *pa = a + f * 3;
     const int c = cnt[gslot];
     int *lst = list + (long)b * NM + off[gslot];
-    __syncthreads();  // the previous list's LDS keys are no longer needed
-    if (c <= kLongSortCap) {
-      int p2 = 1;
-      while (p2 < c) p2 <<= 1;
-      for (int i = tid; i < p2; i += 256) keys[i] = i < c ? lst[i] : 0x7fffffff;
-      __syncthreads();
-      for (int k = 2; k <= p2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-          for (int i = tid; i < p2; i += 256) {
-            const int ixj = i ^ j;
-            if (ixj > i) {
-              const int x = keys[i], y = keys[ixj];
-              const bool up = (i & k) == 0;
-              if ((x > y) == up) {
-                keys[i] = y;
-                keys[ixj] = x;
-              }
-            }
-          }
-          __syncthreads();
-        }
-    } else {
-      if (tid == 0) sort_ints(lst, c);
-      __threadfence_block();
-      __syncthreads();
-    }
+    sort_long_list<256>(lst, c, keys);
     if (tid < 64) {  // wave 0: ordered accumulation
       const CloudLen L = cloud_len<kRagged>(len1, len2, b, N, M);
       const int k = clamp_idx((second ? idx2 : idx1)[f], second ? L.n1 : L.n2);
@@ -536,7 +486,7 @@ __global__ __launch_bounds__(256) void chamfer_bwd_long_kernel(
       for (int base = 0; base < c; base += 64) {
         const int i = base + tid;
         if (i < c) {
-          const long q = (long)b * nb + (c <= kLongSortCap ? keys[i] : lst[i]);
+          const long q = (long)b * nb + sorted_entry(lst, c, keys, i);
           const float *pq = o + q * 3;
           const float gq = gdo[q] * 2;
           terms[0][tid] = gq * (pq[0] - pa[0]);
@@ -556,40 +506,42 @@ __global__ __launch_bounds__(256) void chamfer_bwd_long_kernel(
   }
 }
 
+// sn_chamfer_forward (kRagged = false, len1 = len2 = nullptr) and sn_chamfer_forward_ragged
+template <bool kRagged>
+int chamfer_forward(const char *what, const float *xyz1, const float *xyz2, int b, int n, int m, const int *len1,
+                    const int *len2, float *dist1, int *idx1, float *dist2, int *idx2, void *stream) {
+  SN_REQUIRE(xyz1 && xyz2 && (!kRagged || (len1 && len2)) && dist1 && idx1 && dist2 && idx2, "%s: null pointer", what);
+  SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "%s: need b,n,m >= 1 (got %d,%d,%d)", what, b, n, m);
+  SN_REQUIRE((long)b * n < (1L << 29) && (long)b * m < (1L << 29), "%s: too large", what);
+  // a ragged batch's grid covers the padded widths: a block past its cloud's length writes its padding rows and leaves
+  const int nb1 = sn::ceil_div(n, kQPB), nb2 = sn::ceil_div(m, kQPB);
+  const int nb_max = nb1 > nb2 ? nb1 : nb2;
+  const int clouds_per_xcd = sn::ceil_div(2 * b, 8);
+  const int grid = 8 * clouds_per_xcd * nb_max;
+  hipStream_t s = sn::as_stream(stream);
+  if constexpr (kRagged)
+    SN_TIMED("chamfer_fwd_ragged", s, (chamfer_fwd_kernel<const int *, const int *><<<grid, kThreads, 0, s>>>(
+        xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, nb1, nb2, nb_max, len1, len2)));
+  else
+    SN_TIMED("chamfer_fwd", s, (chamfer_fwd_kernel<><<<grid, kThreads, 0, s>>>(
+        xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, nb1, nb2, nb_max)));
+  return sn::launch_status(what);
+}
+
 }  // namespace
 
 extern "C" int sn_chamfer_forward(const float *xyz1, const float *xyz2, int b, int n, int m,
                                   float *dist1, int *idx1, float *dist2, int *idx2,
                                   void *stream) {
-  SN_REQUIRE(xyz1 && xyz2 && dist1 && idx1 && dist2 && idx2, "sn_chamfer_forward: null pointer");
-  SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "sn_chamfer_forward: need b,n,m >= 1 (got %d,%d,%d)", b, n, m);
-  SN_REQUIRE((long)b * n < (1L << 29) && (long)b * m < (1L << 29), "sn_chamfer_forward: too large");
-  const int nb1 = sn::ceil_div(n, kQPB), nb2 = sn::ceil_div(m, kQPB);
-  const int nb_max = nb1 > nb2 ? nb1 : nb2;
-  const int clouds_per_xcd = sn::ceil_div(2 * b, 8);
-  const int grid = 8 * clouds_per_xcd * nb_max;
-  hipStream_t s = sn::as_stream(stream);
-  SN_TIMED("chamfer_fwd", s, (chamfer_fwd_kernel<><<<grid, kThreads, 0, s>>>(
-      xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, nb1, nb2, nb_max)));
-  return sn::launch_status("sn_chamfer_forward");
+  return chamfer_forward<false>("sn_chamfer_forward", xyz1, xyz2, b, n, m, nullptr, nullptr, dist1, idx1, dist2, idx2,
+                                stream);
 }
 
 extern "C" int sn_chamfer_forward_ragged(const float *xyz1, const float *xyz2, int b, int n, int m,
                                          const int *lengths1, const int *lengths2, float *dist1, int *idx1,
                                          float *dist2, int *idx2, void *stream) {
-  SN_REQUIRE(xyz1 && xyz2 && lengths1 && lengths2 && dist1 && idx1 && dist2 && idx2,
-             "sn_chamfer_forward_ragged: null pointer");
-  SN_REQUIRE(b >= 1 && n >= 1 && m >= 1, "sn_chamfer_forward_ragged: need b,n,m >= 1 (got %d,%d,%d)", b, n, m);
-  SN_REQUIRE((long)b * n < (1L << 29) && (long)b * m < (1L << 29), "sn_chamfer_forward_ragged: too large");
-  // the grid covers the padded widths: a block past its cloud's length writes its padding rows and leaves
-  const int nb1 = sn::ceil_div(n, kQPB), nb2 = sn::ceil_div(m, kQPB);
-  const int nb_max = nb1 > nb2 ? nb1 : nb2;
-  const int clouds_per_xcd = sn::ceil_div(2 * b, 8);
-  const int grid = 8 * clouds_per_xcd * nb_max;
-  hipStream_t s = sn::as_stream(stream);
-  SN_TIMED("chamfer_fwd_ragged", s, (chamfer_fwd_kernel<const int *, const int *><<<grid, kThreads, 0, s>>>(
-      xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, nb1, nb2, nb_max, lengths1, lengths2)));
-  return sn::launch_status("sn_chamfer_forward_ragged");
+  return chamfer_forward<true>("sn_chamfer_forward_ragged", xyz1, xyz2, b, n, m, lengths1, lengths2, dist1, idx1, dist2,
+                               idx2, stream);
 }
 
 extern "C" size_t sn_chamfer_backward_workspace_bytes(int b, int n, int m) {
@@ -642,10 +594,10 @@ int chamfer_backward(const char *what, const float *xyz1, const float *xyz2, con
                                                                 len2);
   // the lists beyond kLongList entries (none in a trained model: the kernel then reads one word and leaves)
   SN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chamfer_bwd_long_kernel<kRagged>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, kLongSortCap * 4));
-  chamfer_bwd_long_kernel<kRagged><<<128, 256, kLongSortCap * 4, s>>>(xyz1, xyz2, graddist1, graddist2, idx1, idx2, b,
-                                                                     n, m, L.cnt, L.off, L.list, L.longs, gradxyz1,
-                                                                     gradxyz2, len1, len2);
+                             hipFuncAttributeMaxDynamicSharedMemorySize, kLongSortCap * (int)sizeof(int)));
+  chamfer_bwd_long_kernel<kRagged><<<kLongBlocks, 256, kLongSortCap * sizeof(int), s>>>(
+      xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m, L.cnt, L.off, L.list, L.longs, gradxyz1, gradxyz2, len1,
+      len2);
   return sn::launch_status(what);
 }
 

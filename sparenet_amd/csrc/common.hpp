@@ -166,7 +166,7 @@ __device__ __forceinline__ float ordered_float(unsigned k) {
 }
 
 // the part of row b of a ragged batch that is points: lengths[b] held to [0, n]; all n rows where lengths is null
-__device__ __forceinline__ int clamped_length(const int *lengths, int b, int n) {
+__host__ __device__ __forceinline__ int clamped_length(const int *lengths, int b, int n) {
   const int len = lengths ? lengths[b] : n;
   return len < 0 ? 0 : (len > n ? n : len);
 }

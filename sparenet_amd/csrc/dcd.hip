@@ -11,8 +11,8 @@
 //   dcd_long_kernel     one workgroup per long list: bitonic sort in LDS up to kLongSortCap entries, in place by one
 //       thread beyond that; the products 256 at a time by the workgroup, the three running sums by three lanes, in order.
 //   dcd_sum_kernel      one workgroup per (cloud, side): the 1024 strided partial sums and their binary tree.
-// chamfer.hip's backward is the model (gather instead of scatter, the same two thresholds); its list builder and sort
-// stay its own.
+// chamfer.hip's backward is the model (gather instead of scatter); the sort of a list, the two thresholds and the rule
+// for long lists are sorted_lists.hpp's, shared with it.
 #include <algorithm>
 #include <cmath>
 #include <cstring>      // the host's memcpy, for sn_expf.h
@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "host_threads.hpp"
 #include "index_lists.hpp"
+#include "sorted_lists.hpp"
 #include "../../include/ops/dcd.h"
 #include "../../include/sn_expf.h"
 
@@ -28,9 +29,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kSumThreads = 1024;    // the loss's partial sums: part of the definition
-constexpr int kLongList = 64;        // inverse lists longer than this are sorted and summed by a workgroup
-constexpr int kLongSortCap = 16384;  // ... in LDS up to this length (64 KiB); longer ones by one thread, in place
-constexpr int kLongBlocks = 128;
 
 enum Power { kPowerZero, kPowerHalf, kPowerOne };      // n_lambda 0, 0.5, 1
 
@@ -40,11 +38,6 @@ struct Rule {
 };
 
 // ---------------------------------------------------------------- the arithmetic of a point, shared by host and device
-__host__ __device__ inline int side_length(const int *lengths, int b, int width) {
-  const int len = lengths ? lengths[b] : width;
-  return len < 0 ? 0 : (len > width ? width : len);
-}
-
 struct PointTerms {
   double term, a;      // 1 - e W and alpha e W / own_len
 };
@@ -101,8 +94,8 @@ __device__ __forceinline__ Point point_of(const Args &a, long e) {
   const int size = a.side[p.s].size;
   p.b = (int)(p.f / size);
   p.i = (int)(p.f - (long)p.b * size);
-  p.own_len = side_length(a.side[p.s].lengths, p.b, size);
-  p.other_len = side_length(a.side[1 - p.s].lengths, p.b, a.side[1 - p.s].size);
+  p.own_len = sn::clamped_length(a.side[p.s].lengths, p.b, size);
+  p.other_len = sn::clamped_length(a.side[1 - p.s].lengths, p.b, a.side[1 - p.s].size);
   p.valid = p.i < p.own_len && p.other_len > 0;
   return p;
 }
@@ -126,41 +119,10 @@ __global__ __launch_bounds__(kThreads) void dcd_point_kernel(Args a) {
     const int k = me.idx[p.f];
     t = k >= 0 && k < p.other_len ? point_terms(a.rule, me.dist[p.f], list_length(other, p.b, k), p.own_len, p.other_len)
                                   : unmatched_terms();
-    if (chosen_by > kLongList && me.grad) a.longs[1 + atomicAdd(&a.longs[0], 1)] = (int)e;
+    if (chosen_by > kLongList && me.grad) register_long_list(a.longs, (int)e);
   }
   me.term[p.f] = t.term;
   me.a[p.f] = t.a;
-}
-
-// in-place ascending sort of an int array in global memory owned by the calling thread
-__device__ inline void sort_list(int *v, int n) {
-  if (n <= 16) {
-    for (int i = 1; i < n; ++i) {
-      const int x = v[i];
-      int j = i - 1;
-      for (; j >= 0 && v[j] > x; --j) v[j + 1] = v[j];
-      v[j + 1] = x;
-    }
-    return;
-  }
-  // heap sort: O(n log n) also when thousands of points share one neighbour
-  auto sift = [&](int root, int end) {
-    for (int child = 2 * root + 1; child <= end; child = 2 * root + 1) {
-      if (child < end && v[child] < v[child + 1]) ++child;
-      if (v[root] >= v[child]) break;
-      const int t = v[root];
-      v[root] = v[child];
-      v[child] = t;
-      root = child;
-    }
-  };
-  for (int start = (n - 2) / 2; start >= 0; --start) sift(start, n - 1);
-  for (int end = n - 1; end > 0; --end) {
-    const int t = v[0];
-    v[0] = v[end];
-    v[end] = t;
-    sift(0, end - 1);
-  }
 }
 
 // the own term of a valid point, per component: 0 where its index names no target (nothing of the other cloud is read)
@@ -188,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void dcd_gather_kernel(Args a) {
   const int c = list_length(me, p.b, p.i);
   if (c > kLongList) return;      // dcd_long_kernel's
   int *lst = me.list + (long)p.b * other.size + list_start(me, p.b, p.i);
-  if (c > 1) sort_list(lst, c);
+  if (c > 1) sort_ints(lst, c);
   const float mine[3] = {me.xyz[p.f * 3], me.xyz[p.f * 3 + 1], me.xyz[p.f * 3 + 2]};
   double acc[3];
   own_terms(a, p, mine, acc);
@@ -210,32 +172,7 @@ __global__ __launch_bounds__(kThreads) void dcd_long_kernel(Args a) {
     const Side &me = a.side[p.s], &other = a.side[1 - p.s];
     const int c = list_length(me, p.b, p.i);
     int *lst = me.list + (long)p.b * other.size + list_start(me, p.b, p.i);
-    const bool in_lds = c <= kLongSortCap;
-    __syncthreads();      // the previous list's keys and terms are no longer needed
-    if (in_lds) {
-      int p2 = 1;
-      while (p2 < c) p2 <<= 1;
-      for (int i = tid; i < p2; i += kThreads) keys[i] = i < c ? lst[i] : 0x7fffffff;
-      __syncthreads();
-      for (int k = 2; k <= p2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-          for (int i = tid; i < p2; i += kThreads) {
-            const int ixj = i ^ j;
-            if (ixj > i) {
-              const int x = keys[i], y = keys[ixj];
-              if ((x > y) == ((i & k) == 0)) {
-                keys[i] = y;
-                keys[ixj] = x;
-              }
-            }
-          }
-          __syncthreads();
-        }
-    } else {
-      if (tid == 0) sort_list(lst, c);
-      __threadfence_block();
-      __syncthreads();
-    }
+    sort_long_list<kThreads>(lst, c, keys);      // its first barrier also stands behind the previous list's terms
     const float *xyz = me.xyz + p.f * 3;
     const float mine[3] = {xyz[0], xyz[1], xyz[2]};
     double own[3];
@@ -244,8 +181,7 @@ __global__ __launch_bounds__(kThreads) void dcd_long_kernel(Args a) {
     for (int base = 0; base < c; base += kThreads) {
       const int t = base + tid;
       if (t < c) {
-        // thread 0's in-place sort is read from memory, not from a line another lane's cache may hold
-        const long q = (long)p.b * other.size + (in_lds ? keys[t] : ((const volatile int *)lst)[t]);
+        const long q = (long)p.b * other.size + sorted_entry(lst, c, keys, t);
         const double cq = other.a[q];
         // list_step's product; its subtraction is taken below, in order
         for (int d = 0; d < 3; ++d) terms[d][tid] = cq * ((double)other.xyz[q * 3 + d] - (double)mine[d]);
@@ -264,8 +200,8 @@ __global__ __launch_bounds__(kSumThreads) void dcd_sum_kernel(Args a) {
   __shared__ double partial[kSumThreads];
   const int b = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
   const Side &me = a.side[s];
-  const int len = side_length(me.lengths, b, me.size);
-  const int other_len = side_length(a.side[1 - s].lengths, b, a.side[1 - s].size);
+  const int len = sn::clamped_length(me.lengths, b, me.size);
+  const int other_len = sn::clamped_length(a.side[1 - s].lengths, b, a.side[1 - s].size);
   double *out = a.sides + (long)b * 2 + s;
   if (len == 0 || other_len == 0) {
     if (tid == 0) *out = 0.0;
@@ -449,9 +385,9 @@ extern "C" int sn_dcd_from_search_host(const float *xyz1, const float *xyz2, con
   parallel_items(b, threads, [&](long c) {
     const size_t o1 = (size_t)c * n, o2 = (size_t)c * m;
     HostSide side[2] = {
-        {xyz1 + o1 * 3, dist1 + o1, idx1 + o1, n, side_length(lengths1, c, n), count1 ? count1 + o1 : nullptr,
+        {xyz1 + o1 * 3, dist1 + o1, idx1 + o1, n, sn::clamped_length(lengths1, c, n), count1 ? count1 + o1 : nullptr,
          gradxyz1 ? gradxyz1 + o1 * 3 : nullptr, {}, {}, {}},
-        {xyz2 + o2 * 3, dist2 + o2, idx2 + o2, m, side_length(lengths2, c, m), count2 ? count2 + o2 : nullptr,
+        {xyz2 + o2 * 3, dist2 + o2, idx2 + o2, m, sn::clamped_length(lengths2, c, m), count2 ? count2 + o2 : nullptr,
          gradxyz2 ? gradxyz2 + o2 * 3 : nullptr, {}, {}, {}}};
     cloud_host(side, rule, sides + (size_t)c * 2);
   });

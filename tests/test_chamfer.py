@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import list_thresholds
 import oracle
 
 
@@ -324,6 +325,29 @@ def test_hip_backward_bit_exact_incl_long_inverse_lists(b, n, m, kind, dev):
     gd1 = rng.random((b, n), dtype=np.float32)
     gd2 = rng.random((b, m), dtype=np.float32)
     _, _, i1, i2 = oracle.chamfer_forward(x, y, mt=True)
+    r1, r2 = oracle.chamfer_backward(x, y, gd1, gd2, i1, i2)
+    _, _, g1, g2 = _run_hip(x, y, gd1, gd2, dev)
+    assert np.array_equal(g1, r1) and np.array_equal(g2, r2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("swap", [False, True], ids=["lists_of_cloud2", "lists_of_cloud1"])
+@pytest.mark.parametrize("counts", list_thresholds.COUNTS, ids=["16_64", "16384"])
+def test_hip_backward_bit_exact_at_list_thresholds(counts, swap, dev):
+    """Inverse lists of exactly 1, 2, 16, 17, 64, 65 and of 16384, 16385 entries: the last length and the first of every
+    regime of sorted_lists.hpp (insertion sort, heap sort, a workgroup's sort in LDS, the in-place fallback), with the
+    lists on the cloud-2 side and, the clouds swapped, on the cloud-1 side -- the two add their own term last and first.
+    With n + m <= 36864 the lists come from the one-workgroup builder; the three-kernel builder, which registers long
+    lists in its scan kernel, is reached by the 30000 + 9000 case of the test above only."""
+    x, y = list_thresholds.clouds(counts)
+    if swap:
+        x, y = y, x
+    rng = np.random.default_rng(len(counts) + swap)
+    gd1 = rng.random(x.shape[:2], dtype=np.float32)
+    gd2 = rng.random(y.shape[:2], dtype=np.float32)
+    _, _, i1, i2 = oracle.chamfer_forward(x, y, mt=True)
+    chosen = i2 if swap else i1      # the queries' choices among the len(counts) targets
+    assert np.array_equal(np.bincount(chosen[0], minlength=len(counts)), counts)
     r1, r2 = oracle.chamfer_backward(x, y, gd1, gd2, i1, i2)
     _, _, g1, g2 = _run_hip(x, y, gd1, gd2, dev)
     assert np.array_equal(g1, r1) and np.array_equal(g2, r2)

@@ -11,6 +11,7 @@ import torch
 
 import dcd_cases as cases
 import dcd_ref as ref
+import list_thresholds
 
 pytestmark = pytest.mark.gpu
 
@@ -151,3 +152,16 @@ def test_fused_validation_metrics_with_dcd(dev):
     for key in plain:
         assert torch.equal(plain[key], flagged[key]), key
     assert torch.equal(flagged["DCD"], density_aware_chamfer(pred, gt, lengths1=lengths1, lengths2=lengths2))
+
+
+@pytest.mark.parametrize("swap", [False, True], ids=["lists_of_cloud2", "lists_of_cloud1"])
+@pytest.mark.parametrize("counts", list_thresholds.COUNTS, ids=["16_64", "16384"])
+def test_list_thresholds(dev, counts, swap):
+    """Lists of exactly 1, 2, 16, 17, 64, 65 and of 16384, 16385 entries (tests/list_thresholds.py), on either side: the
+    device equals the host in sides, counts and both gradients."""
+    x, y = list_thresholds.clouds(counts)
+    if swap:
+        x, y = y, x
+    got = cases.run(x, y, 1000.0, 1.0, "none", dev)
+    assert np.array_equal(got[1]["count1" if swap else "count2"][0], counts)
+    assert_same_bits(got, cases.run(x, y, 1000.0, 1.0, "none", CPU), f"lists of {counts}, device against host")
