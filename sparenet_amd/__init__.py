@@ -18,6 +18,7 @@ _SINKHORN_NAMES = ("sinkhorn_potentials", "sinkhorn_ot", "sinkhorn_divergence", 
 _SWD_NAMES = ("sliced_wasserstein", "sorted_projections", "random_directions", "SlicedWassersteinDistance")
 _DCD_NAMES = ("density_aware_chamfer", "dcd_from_search", "DensityAwareChamferDistance")
 _NORMALS_NAMES = ("local_pca", "surface_variation", "estimate_normals", "normal_consistency", "point_to_plane_chamfer")
+_OCCUPANCY_NAMES = ("occupancy_grid",)
 
 
 def __getattr__(name):
@@ -39,6 +40,10 @@ def __getattr__(name):
         import importlib
 
         return getattr(importlib.import_module("sparenet_amd.cuda.normals"), name)
+    if name in _OCCUPANCY_NAMES:      # the occupancy grid of a set of clouds (sparenet_amd.cuda.occupancy)
+        import importlib
+
+        return getattr(importlib.import_module("sparenet_amd.cuda.occupancy"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

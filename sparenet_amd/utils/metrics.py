@@ -174,6 +174,15 @@ def normal_consistency(pred, gt, k=16, pred_lengths=None, gt_lengths=None, pred_
     return consistency(pred, gt, pred_normals, gt_normals, k, pred_lengths, gt_lengths)
 
 
+def jsd(pred, gt, resolution=28, in_sphere=True, pred_lengths=None, gt_lengths=None, gt_counts=None):
+    """Jensen-Shannon divergence (bits, float64 scalar in [0, 1]) between the occupancy distributions of the SETS pred
+    [N,n,3] and gt [M,m,3] on the resolution^3 grid clipped to the unit sphere
+    (sparenet_amd.utils.set_metrics.jsd_between_sets); `gt_counts` takes gt's grid where it has been computed before."""
+    from sparenet_amd.utils.set_metrics import jsd_between_sets
+
+    return jsd_between_sets(pred, gt, resolution, in_sphere, pred_lengths, gt_lengths, gt_counts)
+
+
 def fpd(pred, gt, model, batch_size=100):
     """Frechet Point-cloud Distance of the SETS pred [N,n,3] and gt [M,m,3] (one scalar, float64) with `model`, a loaded
     sparenet_amd.Frechet.pointnet.PointNetCls(k=16): calculate_fpd on the clouds' own device (the fused PointNet
