@@ -1,6 +1,6 @@
 // block_scan.hpp -- the prefix sums every count / scan / fill chain needs (gfx950 only): the inclusive scan of a wave, and
 // the exclusive scan of a whole workgroup over a sequence of any length, taken in chunks of one value per thread with the
-// running total carried from chunk to chunk in LDS.
+// running total carried from chunk to chunk in LDS.  Also the workgroup's float64 sum in a fixed order (block_sum_f64).
 //
 //   __shared__ alignas(16) sn::BlockScan<1024> scan;    // aligned: the wave sums are then read four words at a time
 //   scan.reset(start);                                  // the sum in front of the first value
@@ -23,6 +23,25 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
     if (lane >= d) v += u;
   }
   return v;
+}
+
+// The float64 sum of one value per thread over a one-dimensional workgroup of kThreads threads, in an order that
+// kThreads alone fixes: a 64-lane xor butterfly (32, 16 .. 1), then the wave sums ascending.  wave_sum: kThreads / kWave
+// doubles of LDS.  Every thread calls it; thread 0 returns the sum (the others their wave's).  One barrier inside,
+// between the waves' writes and thread 0's reads: the caller leaves wave_sum alone until thread 0 has passed a later
+// barrier.
+template <int kThreads>
+__device__ __forceinline__ double block_sum_f64(double acc, double *wave_sum) {
+  static_assert(kThreads % kWave == 0, "whole waves");
+  const int tid = threadIdx.x;
+  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  if ((tid & (kWave - 1)) == 0) wave_sum[tid / kWave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    acc = wave_sum[0];
+    for (int w = 1; w < kThreads / kWave; ++w) acc += wave_sum[w];
+  }
+  return acc;
 }
 
 // Lives in __shared__ memory of a one-dimensional workgroup of kThreads threads; all of them call reset and chunk.

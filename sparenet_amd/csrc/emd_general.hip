@@ -3,27 +3,16 @@
 //
 // The persistent auction of emd.hip is built around n == m, n % 1024 == 0: teams of workgroups own a cloud and wait
 // for each other inside one launch.  This path runs every phase as an ordinary stream-ordered launch, three per
-// iteration, and no workgroup ever waits for another:
-//   bid     every unassigned bidder scans all m targets and finds its top two bid values; the increment goes into the
-//           target's running maximum through an atomic max on an order-preserving integer key (increments can be
-//           negative when eps < 0);
-//   window  the bidders within +-1e-6 of their target's final maximum stamp the target's max_idx with an atomic max
-//           on (iteration << 32 | j): the highest j of this iteration wins, and a target nobody reached keeps its
-//           stale index (the reference never clears max_idx);
-//   assign  winners take their target and evict its previous owner; losers and the evicted append themselves to the
-//           next iteration's list (unordered: which position a bidder gets never enters a result).
-// The next iteration's unassigned count is final when its bid launch starts, so tpu -- and with it the tie rule of
-// the bid -- is read from a settled word.
+// iteration -- bid, window, assign: the steps of emd_auction.hpp over the cloud's rows of the global workspace -- and
+// no workgroup ever waits for another.  The next iteration's unassigned count is final when its bid launch starts, so
+// tpu -- and with it the tie rule of the bid -- is read from a settled word.
 //
 // Bid (the hot path, O(cnt * m) per iteration): a workgroup stages tiles of 1024 targets {x, y, z, A'(price)} in
-// LDS; G lanes serve one bidder (G = 1 while the clouds have many bidders, up to a whole wave when few are left),
-// each lane scans every G-th target of the tile with the conservative fp32 filter of emd_bid.hpp, computes the exact
-// fp64-detour value only where the target can enter its top two, and the group merges its partial results with the
-// (thread(k), k) tie key.  The top-2 VALUES do not depend on the partition, and tie_key restores the reference's
-// index rule, so G is a pure performance choice.
+// LDS; G lanes serve one bidder (G = 1 while the clouds have many bidders, up to a whole wave when few are left) and
+// exchange their filter bound after every tile.
 #include "block_scan.hpp"
 #include "common.hpp"
-#include "emd_bid.hpp"
+#include "emd_auction.hpp"
 
 namespace {
 
@@ -39,14 +28,21 @@ constexpr long kLanesWanted = 1L << 19;
 constexpr int kMaxEltBlocks = 2048;
 
 struct GenWs {
-  float *price;                 // [b, m]
-  int *assign_inv;              // [b, m] bidder holding the target, -1
-  unsigned *max_key;            // [b, m] running maximum increment, as sn::ordered_key
-  unsigned long long *max_idx;  // [b, m] (stamp << 32) | j of the window's winner; stamp = iteration + 1
-  int *bid;                     // [b, n] target of the bidder's last bid
-  float *bid_inc;               // [b, n] its increment
+  float *price;                 // [b, m]  these six: the rows of sn::emd::AuctionRows, cloud after cloud
+  int *assign_inv;              // [b, m]
+  unsigned *max_key;            // [b, m]
+  unsigned long long *max_idx;  // [b, m]
+  int *bid;                     // [b, n]
+  float *bid_inc;               // [b, n]
   int *list[2];                 // [b, n] unassigned bidders of an iteration, any order
   int *cnt[2];                  // [b]    their number
+
+  // cloud i's rows; n and m are the strides
+  __device__ __forceinline__ AuctionRows rows(int i, int n, int m, int *assignment) const {
+    const size_t om = (size_t)i * m, on = (size_t)i * n;
+    return AuctionRows{price + om, assign_inv + om, max_key + om, max_idx + om, bid + on, bid_inc + on,
+                       assignment ? assignment + on : nullptr};
+  }
 };
 
 // lanes per bidder: the power of two <= 64 that gives the launch about kLanesWanted lanes (every cloud is assumed to
@@ -151,10 +147,9 @@ __global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
   if (first / G >= cnt) return;  // uniform over the workgroup
   const int lane = first + (int)threadIdx.x, u = lane / G, sub = lane & (G - 1);
   const bool on = u < cnt;
-  // the reference's geometry: block_cnt = ceil(n / 1024) blocks share the cloud's bidders, tpu threads per bidder
   const CloudSize cs = cloud_size<kRagged>(a.r, i, n, m);  // cnt > 0: the cloud takes part
-  const int block_cnt = (cs.n + 1023) / 1024, per_block = (cnt + block_cnt - 1) / block_cnt;
-  const TieGeom g{cs.m, 1024 / per_block};
+  const TieGeom g = reference_tie_geom(cs.n, cs.m, cnt);
+  const AuctionRows rows = a.w.rows(i, n, m, nullptr);
   int j = 0;
   float x1 = 0.f, y1 = 0.f, z1 = 0.f;
   if (on) {
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
     z1 = p[2];
   }
   const float *p2 = a.xyz2 + (size_t)i * m * 3;
-  const float *price = a.w.price + (size_t)i * m;
+  const float *price = rows.price;
   Top2 t = {-1e9f, -1e9f, -1, -1};
   float cthr = filter_thr(t.better);
   for (int k0 = 0; k0 < cs.m; k0 += kTile) {
@@ -176,54 +171,20 @@ __global__ __launch_bounds__(kGThreads) void emd_general_bid_kernel(BidArgs a) {
       s_t[c] = make_float4(q[0], q[1], q[2], filter_target(price[k0 + c]));
     }
     __syncthreads();
-    if (on) {
-      for (int c = sub; c < tn; c += G) {
-        const float4 q = s_t[c];
-        if (filter_pass(sq_dist(q.x, q.y, q.z, x1, y1, z1), q.w, cthr)) {  // d_k may enter the top two
-          top2_push(t, bid_value(q.x, q.y, q.z, price[k0 + c], x1, y1, z1), k0 + c, g);
-          cthr = fmaxf(cthr, filter_thr(t.better));
-        }
-      }
-    }
-    if (G > 1) {
-      // the second largest of the group's partial top-2 values is a lower bound of the bidder's final `better`:
-      // every lane filters with it (a lane alone would see each of its m / G targets pass about 2 ln(m / G) times)
-      float b1 = t.best, b2 = t.better;
-      for (int off = 1; off < G; off <<= 1) {
-        const float o1 = __shfl_xor(b1, off), o2 = __shfl_xor(b2, off);
-        b2 = fmaxf(fminf(b1, o1), fmaxf(b2, o2));
-        b1 = fmaxf(b1, o1);
-      }
-      cthr = fmaxf(cthr, filter_thr(b2));
-    }
+    if (on) scan_targets(t, cthr, s_t, price, k0, sub, tn, G, x1, y1, z1, g);
+    if (G > 1) cthr = share_filter_bound(t, G, cthr);
   }
-  for (int off = 1; off < G; off <<= 1) {  // butterfly inside the group: every lane ends with the group's result
-    const float ob = __shfl_xor(t.best, off), obb = __shfl_xor(t.better, off);
-    const int oi = __shfl_xor(t.best_i, off), oi2 = __shfl_xor(t.better_i, off);
-    top2_merge(t, ob, obb, oi, oi2, g);
-  }
-  if (on && sub == 0) {
-    const float inc = t.best - t.better + a.eps;
-    const size_t o = (size_t)i * n + j;
-    a.w.bid[o] = t.best_i;
-    a.w.bid_inc[o] = inc;
-    if (t.best_i >= 0)  // -1 only for non-finite inputs: such a bidder never wins
-      atomicMax(&a.w.max_key[(size_t)i * m + t.best_i], sn::ordered_key(inc));
-  }
+  merge_group(t, G, g);
+  if (on && sub == 0) post_bid(rows, j, t, a.eps);
 }
 
 // grid (x, B): GetMax.  Every bidder inside the window of its target's maximum offers (stamp << 32) | j.
 __global__ __launch_bounds__(kGThreads) void emd_general_window_kernel(int n, int m, int cur, unsigned stamp, GenWs w) {
   const int i = blockIdx.y;
   const int cnt = w.cnt[cur][i];
-  for (int u = blockIdx.x * kGThreads + threadIdx.x; u < cnt; u += gridDim.x * kGThreads) {
-    const int j = w.list[cur][(size_t)i * n + u];
-    const int t = w.bid[(size_t)i * n + j];
-    if (t < 0) continue;
-    const size_t ot = (size_t)i * m + t;
-    if (in_window(w.bid_inc[(size_t)i * n + j], sn::ordered_float(w.max_key[ot])))
-      atomicMax(&w.max_idx[ot], ((unsigned long long)stamp << 32) | (unsigned)j);
-  }
+  const AuctionRows rows = w.rows(i, n, m, nullptr);
+  for (int u = blockIdx.x * kGThreads + threadIdx.x; u < cnt; u += gridDim.x * kGThreads)
+    offer_window(rows, w.list[cur][(size_t)i * n + u], stamp);
 }
 
 // grid (x, B): Assign.  Bidders that stay or become unassigned go to the next list (wave-aggregated appends).
@@ -233,42 +194,15 @@ __global__ __launch_bounds__(kGThreads) void emd_general_assign_kernel(int n, in
   const int cnt = w.cnt[cur][i];
   int *next_list = w.list[cur ^ 1] + (size_t)i * n;
   int *next_cnt = &w.cnt[cur ^ 1][i];
+  const AuctionRows rows = w.rows(i, n, m, assignment);
   for (int base = blockIdx.x * kGThreads; base < cnt; base += gridDim.x * kGThreads) {  // uniform over the workgroup
     const int u = base + (int)threadIdx.x;
-    int push = -1;
-    if (u < cnt) {
-      const int j = w.list[cur][(size_t)i * n + u];
-      const int t = w.bid[(size_t)i * n + j];
-      const size_t ot = (size_t)i * m + t;
-      if (t >= 0 && (last || (int)(unsigned)w.max_idx[ot] == j)) {
-        // one winner per target outside the last iteration: the target's words have a single writer
-        assignment[(size_t)i * n + j] = t;
-        if (!last) {
-          const int inv = w.assign_inv[ot];
-          if (inv != -1) {
-            assignment[(size_t)i * n + inv] = -1;
-            push = inv;
-          }
-          w.assign_inv[ot] = j;
-          w.price[ot] += w.bid_inc[(size_t)i * n + j];
-          w.max_key[ot] = sn::ordered_key(-1e9f);
-        }
-      } else if (!last) {
-        push = j;
-      }
-    }
-    const unsigned long long mask = __ballot(push >= 0);
-    if (mask) {
-      const int leader = __ffsll((long long)mask) - 1;
-      int pos = 0;
-      if (lane == leader) pos = atomicAdd(next_cnt, __popcll(mask));
-      pos = __shfl(pos, leader);
-      if (push >= 0) next_list[pos + __popcll(mask & ((1ull << lane) - 1))] = push;
-    }
+    const int push = u < cnt ? settle(rows, w.list[cur][(size_t)i * n + u], last).requeue : -1;
+    append_unassigned(push, lane, next_list, next_cnt);
   }
 }
 
-// CalcDist (emd_cuda.cu:217-226): xyz1 minus xyz2; an unassigned bidder (iters == 0) gets 0
+// CalcDist: every bidder's squared distance to the target it holds
 template <bool kRagged>
 __global__ __launch_bounds__(kGThreads) void emd_general_dist_kernel(int B, int n, int m, const float *__restrict__ xyz1,
                                                                      const float *__restrict__ xyz2,
@@ -283,13 +217,7 @@ __global__ __launch_bounds__(kGThreads) void emd_general_dist_kernel(int B, int 
       }
     }
     const int k = assignment[e];
-    if (k < 0) {
-      dist[e] = 0.f;
-      continue;
-    }
-    const float *p = xyz1 + e * 3, *q = xyz2 + ((e / n) * m + k) * 3;
-    const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-    dist[e] = dx * dx + dy * dy + dz * dz;
+    dist[e] = matched_sq_dist(k, xyz1 + e * 3, xyz2 + ((e / n) * m + k) * 3);
   }
 }
 

@@ -14,14 +14,15 @@
 //     per-point output;
 //   * after each y cloud the 2048 minima are widened to double and added lane -> wave -> workgroup, padding queries
 //     as 0.0, and ONE double is written.
-// Order of the additions: per lane its queries tid + 256 i, i ascending; a 64-lane xor butterfly (32, 16 .. 1); the
-// four wave sums ascending; for n > 2048 the query blocks' partial sums (in the workspace) ascending, by a second
-// small kernel.  All of it, the choice of the instantiation included, is a function of n alone -- not of nx, ny, m, the strip length or the grid -- which is
+// Order of the additions: per lane its queries tid + 256 i, i ascending; sn::block_sum_f64 (a 64-lane xor butterfly,
+// then the four wave sums ascending); for n > 2048 the query blocks' partial sums (in the workspace) ascending, by a
+// second small kernel.  All of it, the choice of the instantiation included, is a function of n alone -- not of nx, ny, m, the strip length or the grid -- which is
 // what makes a matrix entry bit-equal to the 1 x 1 call on its pair.  A minimum over fp32 values has no order.
 //
 // Plain stream-ordered launches: no workgroup waits for another, every loop is bounded by a shape, no floating-point
 // atomics.  Blocks that walk the same strip share their blockIdx % 8 (one XCD's L2 serves the strip): an affinity
 // hint, nothing depends on it.
+#include "block_scan.hpp"
 #include "chamfer_tile.hpp"
 #include "common.hpp"
 #include "../../include/sparenet_hip_ext.h"
@@ -158,12 +159,9 @@ __global__ __launch_bounds__(kThreads) void set_chamfer_kernel(const float *__re
     double acc = 0.0;
 #pragma unroll
     for (int u = 0; u < kQPL; ++u) acc += q0 + u * kThreads < n ? (double)best[u] : 0.0;
-#pragma unroll
-    for (int off = sn::kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((tid & (sn::kWave - 1)) == 0) wsum[tid / sn::kWave] = acc;
-    __syncthreads();
-    // wsum is written again only behind the next cloud's tile barriers, which thread 0 reaches after this read
-    if (tid == 0) out[((size_t)i * ny + j) * nqb + qb] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    // wsum is written again only behind the next cloud's tile barriers, which thread 0 reaches after its reads
+    acc = sn::block_sum_f64<kThreads>(acc, wsum);
+    if (tid == 0) out[((size_t)i * ny + j) * nqb + qb] = acc;
   }
 }
 

@@ -3,22 +3,21 @@
 // x_i for y_j, in float64.  MMD-EMD, COV-EMD and 1-NNA-EMD (sparenet_amd/utils/set_metrics.py) are read off such
 // matrices.
 //
-// The semantics are those of emd_general.hip (bid / window / assign, the (thread(k), k) tie key, the atomic max on the
-// ordered increment key, the 1e-6 window with the highest bidder index winning, a stale window winner for targets
-// nobody reached, the forced assignment of the last iteration), with the arithmetic of emd_bid.hpp.  What differs is
-// where the auction lives: at evaluation size (n <= m <= 2048) the whole state of one pair fits in one CU's LDS, so
+// The auction is that of emd_general.hip, step for step: both run emd_auction.hpp, which states the semantics.  What
+// differs is where the auction lives: at evaluation size (n <= m <= 2048) the whole state of one pair fits in one CU's
+// LDS, so
 //   * ONE workgroup of 1024 lanes runs the entire auction of one pair in one launch, its phases separated by
 //     __syncthreads(); no global workspace, no other workgroup to wait for, nothing to be co-resident with;
 //   * G lanes serve one bidder, G the largest power of two <= 64 that keeps cnt * G within the 1024 lanes, cnt the
-//     workgroup-uniform unassigned count: as the count shrinks the lanes stay busy.  The top-2 VALUES do not depend
-//     on the partition and tie_key restores the reference's index rule, so G never enters a result;
+//     workgroup-uniform unassigned count: as the count shrinks the lanes stay busy;
 //   * the workgroup leaves the iteration loop when its count reaches 0 (every later iteration would be a no-op); the
 //     count is read from LDS behind a barrier, so the exit is uniform;
 //   * after the auction every bidder's dist is evaluated as emd_general_dist_kernel does, its square root is widened
-//     to double, and the terms are added lane (bidders tid, tid + 1024) -> 64-lane xor butterfly (32, 16 .. 1) -> the
-//     16 wave sums ascending: an order that depends on n alone.  ONE double per pair is written.
+//     to double, and the terms are added lane (bidders tid, tid + 1024) -> sn::block_sum_f64: an order that depends
+//     on n alone.  ONE double per pair is written.
+#include "block_scan.hpp"
 #include "common.hpp"
-#include "emd_bid.hpp"
+#include "emd_auction.hpp"
 #include "../../include/sparenet_hip_ext_set_emd.h"
 
 namespace {
@@ -32,16 +31,17 @@ constexpr long kMaxGrid = 0xffffffffL / kThreads;  // workgroups per launch: gri
 constexpr int kGroupSteps = 8;    // targets a lane scans between two exchanges of the group's filter threshold
 
 // The auction state of one pair, carved from the workgroup's dynamic LDS: the one description of its size and places.
+// price .. assignment are the rows of sn::emd::AuctionRows.
 struct SetEmdLds {
   float4 *target;               // [m] x, y, z, filter_target(price)
-  unsigned long long *max_idx;  // [m] (stamp << 32) | j of the window's winner; stamp = iteration + 1
+  unsigned long long *max_idx;  // [m]
   double *wave_sum;             // [kWaves]
   float *price;                 // [m]
-  int *assign_inv;              // [m] bidder holding the target, -1
-  unsigned *max_key;            // [m] running maximum increment, as sn::ordered_key
+  int *assign_inv;              // [m]
+  unsigned *max_key;            // [m]
   float *bidder;                // [n, 3]
-  int *bid;                     // [n] target of the bidder's last bid
-  float *bid_inc;               // [n] its increment
+  int *bid;                     // [n]
+  float *bid_inc;               // [n]
   int *list0, *list1;           // [n] unassigned bidders of an even / odd iteration, any order
   int *assignment;              // [n]
   int *cnt;                     // [2] their number
@@ -111,8 +111,7 @@ __global__ __launch_bounds__(kThreads) void set_emd_kernel(const float *__restri
   }
   __syncthreads();
 
-  // the reference's geometry: block_cnt = ceil(n / 1024) blocks share the cloud's bidders
-  const int block_cnt = (n + 1023) / 1024;
+  const AuctionRows rows{L.price, L.assign_inv, L.max_key, L.max_idx, L.bid, L.bid_inc, L.assignment};
   for (int it = 0; it < iters; ++it) {
     const int cur = it & 1, last = it == iters - 1;
     const int cnt = L.cnt[cur];  // settled behind the barrier that ended the previous assign phase
@@ -121,11 +120,12 @@ __global__ __launch_bounds__(kThreads) void set_emd_kernel(const float *__restri
     const int *list = cur ? L.list1 : L.list0;  // (no array indexed by cur: that would live in scratch)
     int *next_list = cur ? L.list0 : L.list1;
 
-    // ---- bid: G lanes per bidder, kThreads / G bidders per pass
+    // ---- bid: G lanes per bidder, kThreads / G bidders per pass; the resident records are scanned kGroupSteps
+    // targets per lane between two exchanges of the group's filter bound
     {
       const int G = group_lanes(cnt), sub = tid & (G - 1), per_pass = kThreads / G;
       const int tile = G > 1 ? kGroupSteps * G : m;
-      const TieGeom g{m, 1024 / ((cnt + block_cnt - 1) / block_cnt)};
+      const TieGeom g = reference_tie_geom(n, m, cnt);
       for (int u0 = 0; u0 < cnt; u0 += per_pass) {  // uniform over the workgroup
         const int u = u0 + tid / G;
         const bool on = u < cnt;  // uniform over a group
@@ -140,114 +140,45 @@ __global__ __launch_bounds__(kThreads) void set_emd_kernel(const float *__restri
         Top2 t = {-1e9f, -1e9f, -1, -1};
         float cthr = filter_thr(t.better);
         for (int k0 = 0; k0 < m; k0 += tile) {
-          const int k1 = k0 + tile < m ? k0 + tile : m;
-          if (on) {
-            for (int k = k0 + sub; k < k1; k += G) {
-              const float4 q = L.target[k];
-              if (filter_pass(sq_dist(q.x, q.y, q.z, x1, y1, z1), q.w, cthr)) {  // d_k may enter the top two
-                top2_push(t, bid_value(q.x, q.y, q.z, L.price[k], x1, y1, z1), k, g);
-                cthr = fmaxf(cthr, filter_thr(t.better));
-              }
-            }
-          }
-          if (G > 1) {
-            // the second largest of the group's partial top-2 values is a lower bound of the bidder's final `better`
-            float b1 = t.best, b2 = t.better;
-            for (int off = 1; off < G; off <<= 1) {
-              const float o1 = __shfl_xor(b1, off), o2 = __shfl_xor(b2, off);
-              b2 = fmaxf(fminf(b1, o1), fmaxf(b2, o2));
-              b1 = fmaxf(b1, o1);
-            }
-            cthr = fmaxf(cthr, filter_thr(b2));
-          }
+          if (on)  // the resident records are one tile from target 0
+            scan_targets(t, cthr, L.target, L.price, 0, k0 + sub, k0 + tile < m ? k0 + tile : m, G, x1, y1, z1, g);
+          if (G > 1) cthr = share_filter_bound(t, G, cthr);
         }
-        for (int off = 1; off < G; off <<= 1) {  // butterfly inside the group: every lane ends with the group's result
-          const float ob = __shfl_xor(t.best, off), obb = __shfl_xor(t.better, off);
-          const int oi = __shfl_xor(t.best_i, off), oi2 = __shfl_xor(t.better_i, off);
-          top2_merge(t, ob, obb, oi, oi2, g);
-        }
-        if (on && sub == 0) {
-          const float inc = t.best - t.better + eps;
-          L.bid[j] = t.best_i;
-          L.bid_inc[j] = inc;
-          if (t.best_i >= 0)  // -1 only for non-finite inputs: such a bidder never wins
-            atomicMax(&L.max_key[t.best_i], sn::ordered_key(inc));
-        }
+        merge_group(t, G, g);
+        if (on && sub == 0) post_bid(rows, j, t, eps);
       }
     }
     __syncthreads();
 
-    // ---- window: every bidder inside the window of its target's maximum offers (stamp << 32) | j
+    // ---- window
     if (!last) {
-      for (int u = tid; u < cnt; u += kThreads) {
-        const int j = list[u], t = L.bid[j];
-        if (t >= 0 && in_window(L.bid_inc[j], sn::ordered_float(L.max_key[t])))
-          atomicMax(&L.max_idx[t], ((unsigned long long)(unsigned)(it + 1) << 32) | (unsigned)j);
-      }
+      for (int u = tid; u < cnt; u += kThreads) offer_window(rows, list[u], (unsigned)(it + 1));
       __syncthreads();
     }
 
-    // ---- assign: winners take their target and evict its owner; losers and the evicted go to the next list
-    {
-      for (int base = 0; base < cnt; base += kThreads) {  // uniform over the workgroup
-        const int u = base + tid;
-        int push = -1;
-        if (u < cnt) {
-          const int j = list[u], t = L.bid[j];
-          if (t >= 0 && (last || (int)(unsigned)L.max_idx[t] == j)) {
-            // one winner per target outside the last iteration: the target's words have a single writer
-            L.assignment[j] = t;
-            if (!last) {
-              const int inv = L.assign_inv[t];
-              if (inv != -1) {
-                L.assignment[inv] = -1;
-                push = inv;
-              }
-              L.assign_inv[t] = j;
-              const float p = L.price[t] + L.bid_inc[j];
-              L.price[t] = p;
-              L.target[t].w = filter_target(p);
-              L.max_key[t] = sn::ordered_key(-1e9f);
-            }
-          } else if (!last) {
-            push = j;
-          }
-        }
-        const unsigned long long mask = __ballot(push >= 0);
-        if (mask) {
-          const int leader = __ffsll((long long)mask) - 1;
-          int pos = 0;
-          if (lane == leader) pos = atomicAdd(&L.cnt[cur ^ 1], __popcll(mask));
-          pos = __shfl(pos, leader);
-          if (push >= 0) next_list[pos + __popcll(mask & ((1ull << lane) - 1))] = push;
-        }
+    // ---- assign; a winner's record takes the filter word of its new price
+    for (int base = 0; base < cnt; base += kThreads) {  // uniform over the workgroup
+      const int u = base + tid;
+      int push = -1;
+      if (u < cnt) {
+        const Settled s = settle(rows, list[u], last);
+        if (s.target >= 0) L.target[s.target].w = filter_target(s.price);
+        push = s.requeue;
       }
+      append_unassigned(push, lane, next_list, &L.cnt[cur ^ 1]);
     }
     __syncthreads();
   }
 
-  // ---- the pair's number: dist as emd_general_dist_kernel evaluates it (bidder minus target; 0 for an unassigned
-  // bidder), its square root in double, added in the fixed order of the file's header
+  // ---- the pair's number: every bidder's dist, its square root in double, added in the fixed order of the file's header
   double acc = 0.0;
   for (int j = tid; j < n; j += kThreads) {
     const int k = L.assignment[j];
-    float d = 0.f;
-    if (k >= 0) {
-      const float4 q = L.target[k];
-      const float dx = L.bidder[j * 3 + 0] - q.x, dy = L.bidder[j * 3 + 1] - q.y, dz = L.bidder[j * 3 + 2] - q.z;
-      d = dx * dx + dy * dy + dz * dz;
-    }
-    acc += (double)__builtin_sqrtf(d);
+    acc += (double)__builtin_sqrtf(matched_sq_dist(k, L.bidder + j * 3, L.target + k));
     if (assignment) assignment[pair * n + j] = k;
   }
-  for (int off = sn::kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-  if (lane == 0) L.wave_sum[tid / sn::kWave] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = L.wave_sum[0];
-    for (int w = 1; w < kWaves; ++w) s += L.wave_sum[w];
-    sums[pair] = s;
-  }
+  acc = sn::block_sum_f64<kThreads>(acc, L.wave_sum);
+  if (tid == 0) sums[pair] = acc;
 }
 
 }  // namespace
