@@ -23,6 +23,7 @@
 #include "chamfer_tile.hpp"
 #include "common.hpp"
 #include "index_lists.hpp"
+#include "split_launch.hpp"
 #include "../../include/ops/neighbors.h"
 
 namespace {
@@ -32,7 +33,6 @@ using sn::ct::tile_slot;
 
 constexpr int kMaxK = 32;
 constexpr int kWideTile = sn::ct::kTile;   // targets per tile, S == 1
-constexpr int kWideLanes = 256;            // queries per workgroup, S == 1
 constexpr int kSplitTile = 256;            // targets per segment tile, S >= 2
 constexpr int kMaxSplit = 16;              // waves of a 1024-thread workgroup
 constexpr int kWavesPerCu = 16;            // what the dispatch fills the device to before it stops splitting
@@ -315,24 +315,16 @@ __global__ __launch_bounds__(256) void group_bwd_kernel(const float *__restrict_
 // the widest split a list bucket allows: the merge's lists (half the segments write at a time) fit the tiles' LDS
 constexpr int max_split(int kb) { return kb <= 8 ? 16 : (kb <= 16 ? 8 : 4); }
 
-// S: SN_NEIGHBORS_SPLIT when set (held to [1, cap]); otherwise doubled while the launch stays within kWavesPerCu waves
-// per compute unit (four per SIMD) and a segment keeps kMinSegment targets.  A wave's time is its serial walk over
-// n / S targets, so until the device is that full a wider split is faster at every batch size measured (DESIGN.md,
-// "Neighbourhood queries", has the table).
-int pick_split(int b, int n, int m, int cap, int *out) {
-  const char *e = SN_KNOB("SN_NEIGHBORS_SPLIT");
-  if (e && *e) {
-    const int v = atoi(e);
-    *out = v < 1 ? 1 : (v > cap ? cap : v);
-    return 0;
-  }
-  int dev = 0, cus = 0;
-  SN_HIP(hipGetDevice(&dev));
-  SN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const long waves = (long)b * sn::ceil_div(m, 64);
-  int s = 1;
-  while (s * 2 <= cap && waves * s * 2 <= (long)kWavesPerCu * cus && n / (s * 2) >= kMinSegment) s *= 2;
-  *out = s;
+// the launch shape of the m queries of a search against n targets, S at most `cap`: a.split and a.qblocks, workgroups,
+// threads.  kWavesPerCu is four waves per SIMD: until the device is that full a wider split is faster at every batch
+// size measured ("Neighbourhood queries", has the table).
+int search_shape(const char *what, int b, int cap, SearchArgs &a, sn::SplitLaunch *l) {
+  int split = 1;
+  if (const int rc = sn::pick_split(SN_KNOB("SN_NEIGHBORS_SPLIT"), b, a.m, a.n, cap, kWavesPerCu, kMinSegment, &split))
+    return rc;
+  if (const int rc = sn::split_launch(what, b, a.m, split, l)) return rc;
+  a.split = l->split;
+  a.qblocks = l->qblocks;
   return 0;
 }
 
@@ -343,33 +335,20 @@ int check_search(const char *what, const float *xyz, const float *new_xyz, int b
   return 0;
 }
 
-// the launch shape of a search with split S: workgroups, threads
-int search_shape(const char *what, int b, int m, int split, SearchArgs &a, unsigned *grid, unsigned *threads) {
-  const int lanes = split == 1 ? kWideLanes : 64;
-  a.split = split;
-  a.qblocks = sn::ceil_div(m, lanes);
-  SN_REQUIRE((long)b * a.qblocks < (1L << 31), "%s: too many queries", what);
-  *grid = (unsigned)((long)b * a.qblocks);
-  *threads = (unsigned)(lanes * split);
-  return 0;
-}
-
 size_t tile_bytes(int split) { return (size_t)split * (split == 1 ? kWideTile : kSplitTile) * 12; }
 
 template <int KB>
 int launch_knn(SearchArgs a, int b, int k, int *idx, float *dist2, hipStream_t s) {
   constexpr int cap = max_split(KB);
-  int split = 1;
-  if (const int rc = pick_split(b, a.n, a.m, cap, &split)) return rc;
-  unsigned grid = 0, threads = 0;
-  if (const int rc = search_shape("sn_knn_query", b, a.m, split, a, &grid, &threads)) return rc;
-  const size_t merge = (size_t)((split + 1) / 2) * KB * 64 * 8;
-  const size_t lds = split > 1 && merge > tile_bytes(split) ? merge : tile_bytes(split);
-  knn_query_kernel<KB, 64 * cap><<<grid, threads, lds, s>>>(a, k, idx, dist2);
+  sn::SplitLaunch l;
+  if (const int rc = search_shape("sn_knn_query", b, cap, a, &l)) return rc;
+  const size_t merge = (size_t)((l.split + 1) / 2) * KB * 64 * 8;
+  const size_t lds = l.split > 1 && merge > tile_bytes(l.split) ? merge : tile_bytes(l.split);
+  knn_query_kernel<KB, 64 * cap><<<l.grid, l.threads, lds, s>>>(a, k, idx, dist2);
   return sn::launch_status("sn_knn_query");
 }
 
-static_assert(64 * max_split(1) <= 1024 && max_split(kMaxK) * 64 >= kWideLanes, "workgroup sizes of the k-NN buckets");
+static_assert(64 * max_split(1) <= 1024 && max_split(kMaxK) * 64 >= sn::kWideLanes, "workgroup sizes of the k-NN buckets");
 static_assert((kMaxSplit + 1) / 2 * 8 * 64 * 8 <= 48 * 1024 && kMaxSplit * kSplitTile * 12 + kMaxSplit * 64 * 8 <= 64 * 1024,
               "LDS of the widest split");
 
@@ -407,12 +386,10 @@ extern "C" int sn_ball_query(const float *xyz, const float *new_xyz, int b, int 
   SN_REQUIRE((long)m * nsample <= kMaxPoints, "sn_ball_query: m * nsample too large");
   (void)workspace, (void)workspace_bytes;
   SearchArgs a{xyz, new_xyz, lengths, new_lengths, n, m, 1, 1};
-  int split = 1;
-  if (const int rc = pick_split(b, n, m, kMaxSplit, &split)) return rc;
-  unsigned grid = 0, threads = 0;
-  if (const int rc = search_shape("sn_ball_query", b, m, split, a, &grid, &threads)) return rc;
-  const size_t lds = tile_bytes(split) + (split > 1 ? (size_t)split * 64 * 8 : 0);
-  ball_query_kernel<<<grid, threads, lds, sn::as_stream(stream)>>>(a, radius * radius, nsample, pad_first, idx, cnt);
+  sn::SplitLaunch l;
+  if (const int rc = search_shape("sn_ball_query", b, kMaxSplit, a, &l)) return rc;
+  const size_t lds = tile_bytes(l.split) + (l.split > 1 ? (size_t)l.split * 64 * 8 : 0);
+  ball_query_kernel<<<l.grid, l.threads, lds, sn::as_stream(stream)>>>(a, radius * radius, nsample, pad_first, idx, cnt);
   return sn::launch_status("sn_ball_query");
 }
 

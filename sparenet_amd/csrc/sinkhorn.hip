@@ -29,6 +29,7 @@
 // by the shape and S, so two calls give identical bits.
 #include "chamfer_tile.hpp"
 #include "common.hpp"
+#include "split_launch.hpp"
 #include "../../include/ops/sinkhorn.h"
 
 #include <cmath>
@@ -38,7 +39,6 @@ namespace {
 using sn::ct::dist1;
 
 constexpr int kWideTile = 1024;            // targets per tile, S == 1
-constexpr int kWideLanes = 256;            // queries per workgroup, S == 1
 constexpr int kSplitTile = 192;            // targets per segment tile, S >= 2: 16 of them are 48 KiB
 constexpr int kMaxSplit = 16;              // waves of a 1024-thread workgroup
 constexpr int kWavesPerCu = 32;            // what the dispatch fills the device to before it stops splitting
@@ -207,40 +207,17 @@ __global__ __launch_bounds__(1024) void sinkhorn_softmin_kernel(SoftminArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------- dispatch
-// S for nq queries against nt targets: SN_SINKHORN_SPLIT when set (held to [1, kMaxSplit]); otherwise doubled while
-// the launch stays within kWavesPerCu waves per compute unit and a segment keeps kMinSegment targets (DESIGN.md,
-// "Sinkhorn transport", has the sweep).
-int pick_split(int b, int nq, int nt, int *out) {
-  const char *e = SN_KNOB("SN_SINKHORN_SPLIT");
-  if (e && *e) {
-    const int v = atoi(e);
-    *out = v < 1 ? 1 : (v > kMaxSplit ? kMaxSplit : v);
-    return 0;
-  }
-  int dev = 0, cus = 0;
-  SN_HIP(hipGetDevice(&dev));
-  SN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const long waves = (long)b * sn::ceil_div(nq, 64);
-  int s = 1;
-  while (s * 2 <= kMaxSplit && waves * s * 2 <= (long)kWavesPerCu * cus && nt / (s * 2) >= kMinSegment) s *= 2;
-  *out = s;
-  return 0;
-}
-
-struct Side {      // one half-iteration's launch shape
-  int split, qblocks;
-  unsigned grid, threads;
+struct Side : sn::SplitLaunch {      // one half-iteration's launch shape
   size_t lds;
 };
 
+// nq queries against nt targets: S by the shared rule ("Sinkhorn transport", has the sweep)
 int side_of(const char *what, int b, int nq, int nt, Side *s) {
-  if (const int rc = pick_split(b, nq, nt, &s->split)) return rc;
-  const int lanes = s->split == 1 ? kWideLanes : 64;
-  s->qblocks = sn::ceil_div(nq, lanes);
-  SN_REQUIRE((long)b * s->qblocks < (1L << 31), "%s: too many queries", what);
-  s->grid = (unsigned)((long)b * s->qblocks);
-  s->threads = (unsigned)(lanes * s->split);
-  s->lds = (size_t)s->split * (s->split == 1 ? kWideTile : kSplitTile) * 16;
+  int split = 1;
+  if (const int rc = sn::pick_split(SN_KNOB("SN_SINKHORN_SPLIT"), b, nq, nt, kMaxSplit, kWavesPerCu, kMinSegment, &split))
+    return rc;
+  if (const int rc = sn::split_launch(what, b, nq, split, s)) return rc;
+  s->lds = (size_t)split * (split == 1 ? kWideTile : kSplitTile) * 16;
   return 0;
 }
 

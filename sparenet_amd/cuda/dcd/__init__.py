@@ -32,8 +32,8 @@ import torch
 from torch.autograd import Function
 
 from sparenet_amd import _lib
-from sparenet_amd.cuda.chamfer_distance.chamfer_distance import cd
-from sparenet_amd.cuda.ragged import chamfer_ragged_forward_raw, device_lengths
+from sparenet_amd.cuda import _args
+from sparenet_amd.cuda.ragged import chamfer_search_raw
 
 RATIOS = ("none", "size")
 N_LAMBDAS = (0.0, 0.5, 1.0)
@@ -50,35 +50,6 @@ def _check_rule(what, alpha, n_lambda, ratio):
     return float(alpha), float(n_lambda), RATIOS.index(ratio)
 
 
-def _check_pair(what, xyz1, xyz2):
-    for name, t in (("xyz1", xyz1), ("xyz2", xyz2)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.size(2) != 3 or t.size(0) == 0 or t.size(1) == 0:
-            raise ValueError(f"{what}: {name} must be a non-empty [B, N, 3] tensor")
-        if not t.is_floating_point():
-            raise TypeError(f"{what}: {name} must be a floating-point tensor, got {t.dtype}")
-    if xyz1.size(0) != xyz2.size(0):
-        raise ValueError(f"{what}: batch sizes differ ({xyz1.size(0)} and {xyz2.size(0)})")
-    if xyz1.device != xyz2.device:
-        raise ValueError(f"{what}: xyz1 and xyz2 are on different devices")
-
-
-def _search(xyz1, xyz2, lengths1, lengths2):
-    """(dist1, dist2, idx1, idx2, xyz1, xyz2, l1, l2) of the one Chamfer search: contiguous fp32 clouds, int32 lengths
-    on the clouds' device (None, None for a dense batch)."""
-    if lengths1 is not None or lengths2 is not None:
-        b = xyz1.size(0)
-        lengths1 = [xyz1.size(1)] * b if lengths1 is None else lengths1
-        lengths2 = [xyz2.size(1)] * b if lengths2 is None else lengths2
-        return chamfer_ragged_forward_raw(xyz1, xyz2, lengths1, lengths2)
-    xyz1, xyz2 = xyz1.contiguous().float(), xyz2.contiguous().float()
-    b, n, m, dev = xyz1.size(0), xyz1.size(1), xyz2.size(1), xyz1.device
-    dist1, dist2 = torch.empty(b, n, device=dev), torch.empty(b, m, device=dev)
-    idx1 = torch.empty(b, n, dtype=torch.int, device=dev)
-    idx2 = torch.empty(b, m, dtype=torch.int, device=dev)
-    (cd.forward_cuda if xyz1.is_cuda else cd.forward)(xyz1, xyz2, dist1, dist2, idx1, idx2)
-    return dist1, dist2, idx1, idx2, xyz1, xyz2, None, None
-
-
 def dcd_from_search(xyz1, xyz2, dist1, idx1, dist2, idx2, alpha=1000.0, n_lambda=1.0, ratio="none", lengths1=None,
                     lengths2=None, with_grad=True):
     """(sides [B,2] float64, count1 [B,N], count2 [B,M] int32, gradxyz1 [B,N,3], gradxyz2 [B,M,3] fp32) for callers that
@@ -87,18 +58,17 @@ def dcd_from_search(xyz1, xyz2, dist1, idx1, dist2, idx2, alpha=1000.0, n_lambda
     tensors, or CPU tensors throughout (the host entry point).  Not differentiable."""
     what = "dcd_from_search"
     alpha, n_lambda, ratio = _check_rule(what, alpha, n_lambda, ratio)
-    _check_pair(what, xyz1, xyz2)
+    _args.check_pair(what, "xyz1", xyz1, "xyz2", xyz2, same_device=True)
     b, n, m, dev = xyz1.size(0), xyz1.size(1), xyz2.size(1), xyz1.device
     for name, t, width in (("dist1", dist1, n), ("idx1", idx1, n), ("dist2", dist2, m), ("idx2", idx2, m)):
         if not isinstance(t, torch.Tensor) or tuple(t.shape) != (b, width):
             raise ValueError(f"{what}: {name} must be a [{b}, {width}] tensor")
         if t.device != dev:
             raise ValueError(f"{what}: {name} is on {t.device}, the clouds on {dev}")
-    xyz1, xyz2 = xyz1.detach().contiguous().float(), xyz2.detach().contiguous().float()
-    dist1, dist2 = dist1.detach().contiguous().float(), dist2.detach().contiguous().float()
+    xyz1, xyz2, dist1, dist2 = _args.fp32(xyz1), _args.fp32(xyz2), _args.fp32(dist1), _args.fp32(dist2)
     idx1, idx2 = idx1.contiguous().int(), idx2.contiguous().int()
-    l1 = None if lengths1 is None else device_lengths(lengths1, b, n, dev, "lengths1")[0]
-    l2 = None if lengths2 is None else device_lengths(lengths2, b, m, dev, "lengths2")[0]
+    l1 = _args.optional_lengths(lengths1, b, n, dev, "lengths1")
+    l2 = _args.optional_lengths(lengths2, b, m, dev, "lengths2")
     sides = torch.empty(b, 2, dtype=torch.float64, device=dev)
     count1 = torch.empty(b, n, dtype=torch.int32, device=dev)
     count2 = torch.empty(b, m, dtype=torch.int32, device=dev)
@@ -117,7 +87,7 @@ def dcd_from_search(xyz1, xyz2, dist1, idx1, dist2, idx2, alpha=1000.0, n_lambda
 class DensityAwareChamfer(Function):
     @staticmethod
     def forward(ctx, xyz1, xyz2, alpha, n_lambda, ratio, lengths1, lengths2):
-        dist1, dist2, idx1, idx2, x1, x2, l1, l2 = _search(xyz1.detach(), xyz2.detach(), lengths1, lengths2)
+        dist1, dist2, idx1, idx2, x1, x2, l1, l2 = chamfer_search_raw(xyz1.detach(), xyz2.detach(), lengths1, lengths2)
         with_grad = any(ctx.needs_input_grad[:2])
         sides, count1, count2, g1, g2 = dcd_from_search(x1, x2, dist1, idx1, dist2, idx2, alpha, n_lambda, ratio, l1, l2,
                                                         with_grad=with_grad)
@@ -141,7 +111,7 @@ def density_aware_chamfer(xyz1, xyz2, alpha=1000.0, n_lambda=1.0, ratio="none", 
     outputs)."""
     what = "density_aware_chamfer"
     _check_rule(what, alpha, n_lambda, ratio)
-    _check_pair(what, xyz1, xyz2)
+    _args.check_pair(what, "xyz1", xyz1, "xyz2", xyz2, same_device=True)
     value, sides, dist1, dist2, idx1, idx2, count1, count2 = DensityAwareChamfer.apply(
         xyz1, xyz2, alpha, n_lambda, ratio, lengths1, lengths2)
     if not return_raw:

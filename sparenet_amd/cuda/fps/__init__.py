@@ -18,6 +18,7 @@ import torch
 from torch.autograd import Function
 
 from sparenet_amd import _lib
+from sparenet_amd.cuda import _args
 from sparenet_amd.cuda.MDS.MDS_module import gather_operation
 from sparenet_amd.cuda.ragged import device_lengths
 
@@ -53,18 +54,11 @@ def _device_start(start, b, host_lengths, n, dev):
 class FarthestPointSampling(Function):
     @staticmethod
     def forward(ctx, xyz, npoint, lengths, start, return_min_dist):
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.size(2) != 3 or xyz.size(0) == 0 \
-                or xyz.size(1) == 0:
-            raise ValueError("farthest_point_sample: xyz must be a non-empty [B, N, 3] tensor")
-        if not xyz.is_floating_point():
-            raise TypeError(f"farthest_point_sample: xyz must be a floating-point tensor, got {xyz.dtype}")
-        if int(npoint) != npoint or npoint < 1:
-            raise ValueError(f"farthest_point_sample: npoint must be an integer >= 1, got {npoint!r}")
+        _args.check_cloud("farthest_point_sample", "xyz", xyz)
+        npoint = _args.check_count("farthest_point_sample", "npoint", npoint)
         _lib.require_device(xyz, "xyz")      # CPU tensors are refused before anything is uploaded
-        xyz = xyz.contiguous().float()
-        b, n, _ = xyz.shape
-        npoint = int(npoint)
-        dev = xyz.device
+        xyz = _args.fp32(xyz)
+        b, n, dev = xyz.size(0), xyz.size(1), xyz.device
         lens, host_lengths = (None, None) if lengths is None else device_lengths(lengths, b, n, dev, "lengths")
         first = _device_start(start, b, host_lengths, n, dev)
         idx = torch.empty(b, npoint, device=dev, dtype=torch.int32)

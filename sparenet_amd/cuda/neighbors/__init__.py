@@ -24,36 +24,20 @@ import torch
 from torch.autograd import Function
 
 from sparenet_amd import _lib
-from sparenet_amd.cuda.ragged import device_lengths
+from sparenet_amd.cuda import _args
 
 MAX_K = 32
 
 
 def _clouds(what, xyz, new_xyz):
     """The pair as contiguous fp32 device tensors, and (b, n, m)."""
-    for name, t in (("xyz", xyz), ("new_xyz", new_xyz)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.size(2) != 3 or t.size(0) == 0 or t.size(1) == 0:
-            raise ValueError(f"{what}: {name} must be a non-empty [B, N, 3] tensor")
-        if not t.is_floating_point():
-            raise TypeError(f"{what}: {name} must be a floating-point tensor, got {t.dtype}")
-    if xyz.size(0) != new_xyz.size(0):
-        raise ValueError(f"{what}: batch sizes differ ({xyz.size(0)} and {new_xyz.size(0)})")
-    _lib.require_device(xyz, "xyz")      # CPU tensors are refused before anything is uploaded
-    _lib.require_device(new_xyz, "new_xyz")
-    return xyz.contiguous().float(), new_xyz.contiguous().float(), xyz.size(0), xyz.size(1), new_xyz.size(1)
+    _args.check_pair(what, "xyz", xyz, "new_xyz", new_xyz, device="contiguous")
+    return _args.fp32(xyz), _args.fp32(new_xyz), xyz.size(0), xyz.size(1), new_xyz.size(1)
 
 
 def _lengths(lengths, new_lengths, b, n, m, dev):
-    lens = None if lengths is None else device_lengths(lengths, b, n, dev, "lengths")[0]
-    new_lens = None if new_lengths is None else device_lengths(new_lengths, b, m, dev, "new_lengths")[0]
-    return lens, new_lens
-
-
-def _count(what, name, v, top=None):
-    if int(v) != v or v < 1 or (top is not None and v > top):
-        limit = "" if top is None else f" and <= {top}"
-        raise ValueError(f"{what}: {name} must be an integer >= 1{limit}, got {v!r}")
-    return int(v)
+    return (_args.optional_lengths(lengths, b, n, dev, "lengths"),
+            _args.optional_lengths(new_lengths, b, m, dev, "new_lengths"))
 
 
 class BallQuery(Function):
@@ -61,7 +45,7 @@ class BallQuery(Function):
     def forward(ctx, radius, nsample, xyz, new_xyz, lengths, new_lengths, pad, return_count):
         if pad not in ("first", "none"):
             raise ValueError(f"ball_query: pad must be 'first' or 'none', got {pad!r}")
-        nsample = _count("ball_query", "nsample", nsample)
+        nsample = _args.check_count("ball_query", "nsample", nsample)
         radius = float(radius)
         if not 0.0 <= radius < float("inf"):
             raise ValueError(f"ball_query: radius must be finite and >= 0, got {radius!r}")
@@ -86,7 +70,7 @@ class BallQuery(Function):
 class KnnQuery(Function):
     @staticmethod
     def forward(ctx, k, xyz, new_xyz, lengths, new_lengths):
-        k = _count("knn_query", "k", k, MAX_K)
+        k = _args.check_count("knn_query", "k", k, MAX_K)
         xyz, new_xyz, b, n, m = _clouds("knn_query", xyz, new_xyz)
         lens, new_lens = _lengths(lengths, new_lengths, b, n, m, xyz.device)
         idx = torch.empty(b, m, k, device=xyz.device, dtype=torch.int32)
@@ -140,8 +124,8 @@ def _gather_args(what, features, idx, weight=None):
     _lib.require_device(idx, "idx")
     if weight is not None:
         _lib.require_device(weight, "weight")
-        weight = weight.detach().contiguous().float()
-    return features.contiguous().float(), idx.to(torch.int32).contiguous(), weight
+        weight = _args.fp32(weight)
+    return _args.fp32(features), idx.to(torch.int32).contiguous(), weight
 
 
 def _backward(ctx, grad_out):

@@ -21,7 +21,8 @@ import torch
 from torch.autograd import Function
 
 from sparenet_amd import _lib
-from sparenet_amd.cuda.ragged import valid_mask
+from sparenet_amd.cuda import _args
+from sparenet_amd.cuda.ragged import chamfer_search_raw, mean_over_mask, valid_mask
 
 MAX_K = 64
 
@@ -40,10 +41,7 @@ class LocalPca(Function):
     @staticmethod
     def forward(ctx, xyz, idx, new_xyz, viewpoint, return_frames):
         what = "local_pca"
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.size(2) != 3 or xyz.size(0) == 0 or xyz.size(1) == 0:
-            raise ValueError(f"{what}: xyz must be a non-empty [B, N, 3] tensor")
-        if not xyz.is_floating_point():
-            raise TypeError(f"{what}: xyz must be a floating-point tensor, got {xyz.dtype}")
+        _args.check_cloud(what, "xyz", xyz)
         if not isinstance(idx, torch.Tensor) or idx.dtype not in (torch.int32, torch.int64):
             raise TypeError(f"{what}: idx must be an int32 / int64 tensor")
         b, n = xyz.size(0), xyz.size(1)
@@ -63,8 +61,8 @@ class LocalPca(Function):
                 raise ValueError(f"{what}: new_xyz must be a [{b}, {m}, 3] tensor")
             if new_xyz.device != xyz.device:
                 raise ValueError(f"{what}: new_xyz is on {new_xyz.device}, xyz on {xyz.device}")
-            new_xyz = new_xyz.detach().contiguous().float()
-        xyz, idx, dev = xyz.detach().contiguous().float(), idx.to(torch.int32).contiguous(), xyz.device
+            new_xyz = _args.fp32(new_xyz)
+        xyz, idx, dev = _args.fp32(xyz), idx.to(torch.int32).contiguous(), xyz.device
         normals = torch.empty(b, m, 3, device=dev)
         eigenvalues = torch.empty(b, m, 3, dtype=torch.float64, device=dev)
         frames = torch.empty(b, m, 3, 3, device=dev) if return_frames else None
@@ -126,20 +124,13 @@ def _rows_of(t, idx):
     return torch.gather(t, 1, idx.clamp_min(0).long()[:, :, None].expand(-1, -1, t.size(2)))
 
 
-def _masked_mean64(values, mask):
-    """[B] float64: the sum of the float64 values at `mask` over their number, 0 where there is none."""
-    total = torch.where(mask, values, torch.zeros((), dtype=values.dtype, device=values.device)).sum(dim=1)
-    count = mask.sum(dim=1)
-    return torch.where(count > 0, total / count.clamp_min(1), torch.zeros_like(total))
-
-
 def normal_consistency_from_search(idx1, idx2, normals1, normals2, lengths1=None, lengths2=None):
     """[B] fp32 from the Chamfer search's idx1 [B,N] / idx2 [B,M] and the normals of both clouds: for callers that hold
     the search already.  lengths as int32 tensors on the normals' device (or None)."""
     n1, n2 = normals1.detach().double(), normals2.detach().double()
     v1, v2 = _valid_rows(idx1, lengths1, n1.size(1)), _valid_rows(idx2, lengths2, n2.size(1))
-    side1 = _masked_mean64((n1 * _rows_of(n2, idx1)).sum(dim=2).abs(), v1)
-    side2 = _masked_mean64((n2 * _rows_of(n1, idx2)).sum(dim=2).abs(), v2)
+    side1 = mean_over_mask((n1 * _rows_of(n2, idx1)).sum(dim=2).abs(), v1)
+    side2 = mean_over_mask((n2 * _rows_of(n1, idx2)).sum(dim=2).abs(), v2)
     return (0.5 * (side1 + side2)).float()
 
 
@@ -160,13 +151,11 @@ def normal_consistency(xyz1, xyz2, normals1=None, normals2=None, k=16, lengths1=
     valid rows, rounded once.  Missing normals are estimated with estimate_normals(., k) (device tensors only; with
     both normals given CPU tensors work too).  `lengths1` / `lengths2` make the batch ragged; a pair with an empty
     side gives 0.  Not differentiable."""
-    from sparenet_amd.cuda.dcd import _check_pair, _search
-
     what = "normal_consistency"
-    _check_pair(what, xyz1, xyz2)
+    _args.check_pair(what, "xyz1", xyz1, "xyz2", xyz2, same_device=True)
     normals1 = _normals_of(what, "normals1", normals1, xyz1, k, lengths1)
     normals2 = _normals_of(what, "normals2", normals2, xyz2, k, lengths2)
-    _, _, idx1, idx2, _, _, l1, l2 = _search(xyz1.detach(), xyz2.detach(), lengths1, lengths2)
+    _, _, idx1, idx2, _, _, l1, l2 = chamfer_search_raw(xyz1.detach(), xyz2.detach(), lengths1, lengths2)
     return normal_consistency_from_search(idx1, idx2, normals1, normals2, l1, l2)
 
 
@@ -188,14 +177,12 @@ def point_to_plane_chamfer(xyz1, xyz2, normals2, lengths1=None, lengths2=None):
     grouping_operation's: accurate to the bound of an fp32 sum of the list's terms, NOT bit-reproducible (as
     include/ops/neighbors.h says of its own).  `lengths1` / `lengths2` make the batch ragged: padding rows are never
     read into the value and get gradient 0; a pair with an empty side gives 0."""
-    from sparenet_amd.cuda.dcd import _check_pair, _search
-
     what = "point_to_plane_chamfer"
-    _check_pair(what, xyz1, xyz2)
+    _args.check_pair(what, "xyz1", xyz1, "xyz2", xyz2, same_device=True)
     if normals2 is None:
         raise ValueError(f"{what}: normals2, the normals of xyz2, are required")
     normals = _normals_of(what, "normals2", normals2, xyz2, None, None).detach().float()
-    _, _, idx1, idx2, _, _, l1, l2 = _search(xyz1.detach(), xyz2.detach(), lengths1, lengths2)
+    _, _, idx1, idx2, _, _, l1, l2 = chamfer_search_raw(xyz1.detach(), xyz2.detach(), lengths1, lengths2)
     v1, v2 = _valid_rows(idx1, l1, xyz1.size(1)), _valid_rows(idx2, l2, xyz2.size(1))
     zero = torch.zeros((), device=xyz1.device)
     x, y = xyz1.float(), xyz2.float()

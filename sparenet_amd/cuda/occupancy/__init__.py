@@ -16,7 +16,7 @@ differentiable; inputs are detached.
 import torch
 
 from sparenet_amd import _lib
-from sparenet_amd.cuda.ragged import device_lengths
+from sparenet_amd.cuda import _args
 
 MIN_RESOLUTION, MAX_RESOLUTION = 2, 32
 
@@ -25,18 +25,14 @@ def occupancy_grid(clouds, resolution=28, in_sphere=True, lengths=None, return_c
     """(counts [res,res,res] int64, occupied [res,res,res] int32[, cells [S,n] int32]) of the set clouds [S,n,3] (see
     the module's text).  Device tensors go through the kernel, CPU tensors through the host entry point."""
     what = "occupancy_grid"
-    if not isinstance(clouds, torch.Tensor) or clouds.dim() != 3 or clouds.size(2) != 3 or clouds.size(0) == 0 \
-            or clouds.size(1) == 0:
-        raise ValueError(f"{what}: clouds must be a non-empty [S, n, 3] tensor")
-    if not clouds.is_floating_point():
-        raise TypeError(f"{what}: clouds must be a floating-point tensor, got {clouds.dtype}")
+    _args.check_cloud(what, "clouds", clouds, "[S, n, 3]")
     res = int(resolution)
     if res != resolution or not MIN_RESOLUTION <= res <= MAX_RESOLUTION:
         raise ValueError(f"{what}: resolution must be an integer in {MIN_RESOLUTION}..{MAX_RESOLUTION}, got {resolution!r}")
-    xyz, dev = clouds.detach().contiguous().float(), clouds.device
+    xyz, dev = _args.fp32(clouds), clouds.device
     s, n = xyz.size(0), xyz.size(1)
     sphere = 1 if in_sphere else 0
-    lens = None if lengths is None else device_lengths(lengths, s, n, dev, "lengths")[0]
+    lens = _args.optional_lengths(lengths, s, n, dev, "lengths")
     counts = torch.empty(res, res, res, dtype=torch.int64, device=dev)
     occupied = torch.empty(res, res, res, dtype=torch.int32, device=dev)
     cells = torch.empty(s, n, dtype=torch.int32, device=dev) if return_cells else None

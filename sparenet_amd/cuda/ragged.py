@@ -8,6 +8,7 @@ dense op gives for that cloud alone, bit for bit, whatever else is in the batch.
     pad_compact(xyz)                               -> packed, lengths, src    zero rows (the reference's padding) -> ragged
     chamfer_ragged(xyz1, xyz2, lengths1, lengths2) -> dist1, dist2
     emd_ragged(xyz1, xyz2, lengths1, lengths2, eps, iters) -> dist, assignment    needs lengths1 <= lengths2 per cloud
+    chamfer_search_raw(xyz1, xyz2, lengths1=None, lengths2=None) -> the one search, dense or ragged, without autograd
     masked_mean(dist, lengths)                     -> [B]
 
 `lengths` is an int32 / int64 tensor on any device, or a list.  Host values are range-checked and uploaded; a device
@@ -136,6 +137,24 @@ def chamfer_ragged_forward_raw(xyz1, xyz2, lengths1, lengths2):
     return dist1, dist2, idx1, idx2, xyz1, xyz2, l1, l2
 
 
+def chamfer_search_raw(xyz1, xyz2, lengths1=None, lengths2=None):
+    """(dist1, dist2, idx1, idx2, xyz1, xyz2, l1, l2) of the one Chamfer search of a pair, without autograd: a dense
+    batch through cd.forward_cuda (CPU tensors: the host Chamfer) with l1 = l2 = None, a ragged one -- either lengths
+    given; None = every row -- through chamfer_ragged_forward_raw.  The clouds come back contiguous and fp32."""
+    if lengths1 is not None or lengths2 is not None:
+        b = xyz1.size(0)
+        lengths1 = [xyz1.size(1)] * b if lengths1 is None else lengths1
+        lengths2 = [xyz2.size(1)] * b if lengths2 is None else lengths2
+        return chamfer_ragged_forward_raw(xyz1, xyz2, lengths1, lengths2)
+    xyz1, xyz2 = xyz1.contiguous().float(), xyz2.contiguous().float()
+    b, n, m, dev = xyz1.size(0), xyz1.size(1), xyz2.size(1), xyz1.device
+    dist1, dist2 = torch.empty(b, n, device=dev), torch.empty(b, m, device=dev)
+    idx1 = torch.empty(b, n, dtype=torch.int, device=dev)
+    idx2 = torch.empty(b, m, dtype=torch.int, device=dev)
+    (cd.forward_cuda if xyz1.is_cuda else cd.forward)(xyz1, xyz2, dist1, dist2, idx1, idx2)
+    return dist1, dist2, idx1, idx2, xyz1, xyz2, None, None
+
+
 class ChamferRaggedFunction(Function):
     @staticmethod
     def forward(ctx, xyz1, xyz2, lengths1, lengths2):
@@ -221,10 +240,15 @@ def valid_mask(lengths, width, device):
     return torch.arange(width, device=device)[None, :] < lengths.to(device)[:, None]
 
 
+def mean_over_mask(values, mask):
+    """[B] float64: the sum of the float64 `values` [B, W] at the bool `mask` over their number, 0 where there is
+    none."""
+    total = torch.where(mask, values, torch.zeros((), dtype=torch.float64, device=values.device)).sum(dim=1)
+    count = mask.sum(dim=1)
+    return torch.where(count > 0, total / count.clamp_min(1), torch.zeros_like(total))
+
+
 def masked_mean(dist, lengths):
     """[B]: the sum of dist[i, :lengths[i]] divided by lengths[i], 0 for an empty cloud.  Accumulated in float64 and
     rounded once to dist's dtype, so the padded width does not enter the value; padding rows are not read into it."""
-    mask = valid_mask(lengths, dist.size(1), dist.device)
-    total = torch.where(mask, dist.double(), torch.zeros((), dtype=torch.float64, device=dist.device)).sum(dim=1)
-    count = mask.sum(dim=1)
-    return torch.where(count > 0, total / count.clamp_min(1), torch.zeros_like(total)).to(dist.dtype)
+    return mean_over_mask(dist.double(), valid_mask(lengths, dist.size(1), dist.device)).to(dist.dtype)

@@ -33,7 +33,8 @@ import torch
 from torch.autograd import Function
 
 from sparenet_amd import _lib
-from sparenet_amd.cuda.ragged import device_lengths
+from sparenet_amd.cuda import _args
+from sparenet_amd.cuda.ragged import valid_mask
 
 DEFAULT_ITERS = 20      # without an eps_start
 EXTRA_ITERS = 5         # steps at the final eps behind an annealed schedule
@@ -62,9 +63,7 @@ def _params(what, eps, iters, eps_start, decay):
             while eps_start * decay ** reach > eps:
                 reach += 1
             iters = reach + EXTRA_ITERS
-    elif isinstance(iters, bool) or int(iters) != iters or iters < 1:
-        raise ValueError(f"{what}: iters must be an integer >= 1, got {iters!r}")
-    return eps, int(iters), eps_start, decay
+    return eps, _args.check_count(what, "iters", iters, refuse_bool=True), eps_start, decay
 
 
 def schedule(eps, iters=None, eps_start=None, decay=0.5):
@@ -76,22 +75,13 @@ def schedule(eps, iters=None, eps_start=None, decay=0.5):
 
 def _clouds(what, x, y):
     """The pair as contiguous fp32 device tensors, and (b, n, m)."""
-    for name, t in (("x", x), ("y", y)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.size(2) != 3 or t.size(0) == 0 or t.size(1) == 0:
-            raise ValueError(f"{what}: {name} must be a non-empty [B, N, 3] tensor")
-        if not t.is_floating_point():
-            raise TypeError(f"{what}: {name} must be a floating-point tensor, got {t.dtype}")
-    if x.size(0) != y.size(0):
-        raise ValueError(f"{what}: batch sizes differ ({x.size(0)} and {y.size(0)})")
-    _lib.require_device(x, "x")      # CPU tensors are refused before anything is uploaded
-    _lib.require_device(y, "y")
-    return x.detach().contiguous().float(), y.detach().contiguous().float(), x.size(0), x.size(1), y.size(1)
+    _args.check_pair(what, "x", x, "y", y, device="contiguous")
+    return _args.fp32(x), _args.fp32(y), x.size(0), x.size(1), y.size(1)
 
 
 def _lengths(x_lengths, y_lengths, b, n, m, dev):
-    lx = None if x_lengths is None else device_lengths(x_lengths, b, n, dev, "x_lengths")[0]
-    ly = None if y_lengths is None else device_lengths(y_lengths, b, m, dev, "y_lengths")[0]
-    return lx, ly
+    return (_args.optional_lengths(x_lengths, b, n, dev, "x_lengths"),
+            _args.optional_lengths(y_lengths, b, m, dev, "y_lengths"))
 
 
 def _solve(x, y, b, n, m, lx, ly, eps, iters, eps_start, decay, g0=None):
@@ -140,8 +130,7 @@ class SinkhornOT(Function):
         lx, ly = _lengths(x_lengths, y_lengths, b, n, m, x.device)
         f, g = _solve(x, y, b, n, m, lx, ly, eps, iters, eps_start, decay)
         cx, cy = _counts(lx, b, n, x.device), _counts(ly, b, m, x.device)
-        mask_x = torch.arange(n, device=x.device)[None, :] < cx[:, None]
-        mask_y = torch.arange(m, device=x.device)[None, :] < cy[:, None]
+        mask_x, mask_y = valid_mask(cx, n, x.device), valid_mask(cy, m, x.device)
         zero = torch.zeros((), dtype=torch.float64, device=x.device)
         total = (torch.where(mask_x, f.double(), zero).sum(dim=1) / cx.clamp_min(1)
                  + torch.where(mask_y, g.double(), zero).sum(dim=1) / cy.clamp_min(1))
@@ -161,7 +150,7 @@ class SinkhornOT(Function):
 
         def side(q, t, pot, nq, nt, lq, lt, cq):
             bary = _barycenter(q, t, pot, b, nq, nt, lq, lt, ctx.eps)
-            live = (torch.arange(nq, device=q.device)[None, :] < cq[:, None]) & both[:, None]
+            live = valid_mask(cq, nq, q.device) & both[:, None]
             scale = (2.0 * grad / cq.clamp_min(1)).float()
             return torch.where(live[:, :, None], scale[:, None, None] * (q - bary), torch.zeros((), device=q.device))
 
@@ -183,10 +172,8 @@ def sinkhorn_divergence(x, y, eps, iters=None, eps_start=None, decay=0.5, x_leng
     _clouds("sinkhorn_divergence", x, y)
     b, n, m = x.size(0), x.size(1), y.size(1)
     width = max(n, m)
-    lx = _counts(None if x_lengths is None else device_lengths(x_lengths, b, n, x.device, "x_lengths")[0], b, n,
-                 x.device)
-    ly = _counts(None if y_lengths is None else device_lengths(y_lengths, b, m, x.device, "y_lengths")[0], b, m,
-                 x.device)
+    lx, ly = _lengths(x_lengths, y_lengths, b, n, m, x.device)
+    lx, ly = _counts(lx, b, n, x.device), _counts(ly, b, m, x.device)
     xp = torch.nn.functional.pad(x.float(), (0, 0, 0, width - n))
     yp = torch.nn.functional.pad(y.float(), (0, 0, 0, width - m))
     ot = sinkhorn_ot(torch.cat([xp, xp, yp]), torch.cat([yp, xp, yp]), eps, iters, eps_start, decay,

@@ -26,7 +26,7 @@ import torch
 from torch.autograd import Function
 
 from sparenet_amd import _lib
-from sparenet_amd.cuda.ragged import device_lengths
+from sparenet_amd.cuda import _args
 
 MAX_POINTS = 16384
 REDUCTIONS = ("mean", "max")
@@ -35,30 +35,11 @@ REDUCTIONS = ("mean", "max")
 def random_directions(n_slices, device, generator=None):
     """[n_slices, 3] fp32 unit vectors on `device`: Gaussians from `generator` (its device decides where they are
     drawn), normalised."""
-    if isinstance(n_slices, bool) or int(n_slices) != n_slices or n_slices < 1:
-        raise ValueError(f"random_directions: n_slices must be an integer >= 1, got {n_slices!r}")
+    n_slices = _args.check_count("random_directions", "n_slices", n_slices, refuse_bool=True)
     where = generator.device if generator is not None else device
-    g = torch.randn(int(n_slices), 3, generator=generator, device=where, dtype=torch.float32)
+    g = torch.randn(n_slices, 3, generator=generator, device=where, dtype=torch.float32)
     g = g / g.norm(dim=1, keepdim=True).clamp_min(1e-30)
     return g.to(device)
-
-
-def _on_device(t, name):
-    """CPU tensors are refused, with the message of a device entry point, before anything is uploaded or allocated; a
-    device tensor of any layout passes (the wrappers make it contiguous)."""
-    if not t.is_cuda:
-        _lib.require_device(t, name)
-
-
-def _cloud(what, name, t, device=True):
-    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.size(2) != 3 or t.size(0) == 0 or t.size(1) == 0:
-        raise ValueError(f"{what}: {name} must be a non-empty [B, N, 3] tensor")
-    if not t.is_floating_point():
-        raise TypeError(f"{what}: {name} must be a floating-point tensor, got {t.dtype}")
-    if t.size(1) > MAX_POINTS:
-        raise ValueError(f"{what}: {name} has {t.size(1)} points per cloud, at most {MAX_POINTS} are supported")
-    if device:
-        _on_device(t, name)
 
 
 def _directions(what, directions, b, dev):
@@ -69,7 +50,7 @@ def _directions(what, directions, b, dev):
         raise ValueError(f"{what}: directions must be a floating-point [L, 3] or [B, L, 3] tensor")
     if d.dim() == 3 and d.size(0) != b:
         raise ValueError(f"{what}: directions [B, L, 3] must have B = {b}, got {d.size(0)}")
-    _on_device(d, "directions")
+    _args.on_device(d, "directions")
     return d.detach().to(dev).float().contiguous(), d.size(-2), int(d.dim() == 3)
 
 
@@ -83,11 +64,12 @@ def sorted_projections(x, dirs, lengths=None):
     """(values [B, L, N] fp32, perm [B, L, N] int32): every cloud's projections onto every direction in ascending
     order and the point index at each rank -- the stable order, ties by index.  Ranks past a cloud's length hold +inf
     and -1.  Not differentiable."""
-    _cloud("sorted_projections", "x", x)
+    _args.check_cloud("sorted_projections", "x", x, max_points=MAX_POINTS)
+    _args.on_device(x, "x")
     b, n = x.size(0), x.size(1)
     d, slices, per_cloud = _directions("sorted_projections", dirs, b, x.device)
-    x = x.detach().contiguous().float()
-    ln = None if lengths is None else device_lengths(lengths, b, n, x.device, "lengths")[0]
+    x = _args.fp32(x)
+    ln = _args.optional_lengths(lengths, b, n, x.device, "lengths")
     values = torch.empty(b, slices, n, device=x.device)
     perm = torch.empty(b, slices, n, dtype=torch.int32, device=x.device)
     _lib.op_call("swd", "sn_swd_project_sort", x, d, b, n, slices, per_cloud, ln, values, perm)
@@ -111,9 +93,9 @@ class SlicedWasserstein(Function):
         what = "sliced_wasserstein"
         b, n, m = x.size(0), x.size(1), y.size(1)
         d, slices, per_cloud = _directions(what, directions, b, x.device)
-        lx = None if x_lengths is None else device_lengths(x_lengths, b, n, x.device, "x_lengths")[0]
-        ly = None if y_lengths is None else device_lengths(y_lengths, b, m, x.device, "y_lengths")[0]
-        xf, yf = x.detach().contiguous().float(), y.detach().contiguous().float()
+        lx = _args.optional_lengths(x_lengths, b, n, x.device, "x_lengths")
+        ly = _args.optional_lengths(y_lengths, b, m, x.device, "y_lengths")
+        xf, yf = _args.fp32(x), _args.fp32(y)
         with_grad = any(ctx.needs_input_grad[:2])
         if reduction == "mean":
             cost, gx, gy = _forward(xf, yf, d, slices, per_cloud, lx, ly, p, with_grad)
@@ -144,14 +126,7 @@ def sliced_wasserstein(x, y, n_slices=128, p=2, directions=None, generator=None,
     p = _check_p(what, p)
     if reduction not in REDUCTIONS:
         raise ValueError(f"{what}: reduction must be one of {', '.join(REDUCTIONS)}, got {reduction!r}")
-    _cloud(what, "x", x, device=False)
-    _cloud(what, "y", y, device=False)
-    if x.size(0) != y.size(0):
-        raise ValueError(f"{what}: batch sizes differ ({x.size(0)} and {y.size(0)})")
-    _on_device(x, "x")
-    _on_device(y, "y")
-    if x.device != y.device:
-        raise ValueError(f"{what}: x and y are on different devices")
+    _args.check_pair(what, "x", x, "y", y, device="any", same_device=True, max_points=MAX_POINTS)
     if directions is None:
         directions = random_directions(n_slices, x.device, generator)
     return SlicedWasserstein.apply(x, y, directions, p, x_lengths, y_lengths, reduction)
@@ -162,11 +137,10 @@ class SlicedWassersteinDistance(torch.nn.Module):
 
     def __init__(self, n_slices=128, p=2, reduction="mean"):
         super().__init__()
-        if isinstance(n_slices, bool) or int(n_slices) != n_slices or n_slices < 1:
-            raise ValueError(f"SlicedWassersteinDistance: n_slices must be an integer >= 1, got {n_slices!r}")
+        n_slices = _args.check_count("SlicedWassersteinDistance", "n_slices", n_slices, refuse_bool=True)
         if reduction not in REDUCTIONS:
             raise ValueError(f"SlicedWassersteinDistance: reduction must be one of {', '.join(REDUCTIONS)}")
-        self.n_slices, self.p, self.reduction = int(n_slices), _check_p("SlicedWassersteinDistance", p), reduction
+        self.n_slices, self.p, self.reduction = n_slices, _check_p("SlicedWassersteinDistance", p), reduction
 
     def forward(self, x, y, directions=None, generator=None, x_lengths=None, y_lengths=None):
         return sliced_wasserstein(x, y, self.n_slices, self.p, directions, generator, x_lengths, y_lengths,

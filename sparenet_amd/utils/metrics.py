@@ -13,9 +13,11 @@ double on the same fp32 coordinates: the two can only disagree for |d - th| ~ 1e
 """
 import torch
 
+from sparenet_amd.cuda import _args
 from sparenet_amd.cuda.chamfer_distance.chamfer_distance import ChamferDistanceFunction
 from sparenet_amd.cuda.emd.emd_general import emd_general
 from sparenet_amd.cuda.emd.emd_module import emdModule
+from sparenet_amd.cuda.ragged import chamfer_search_raw
 from sparenet_amd.utils.set_metrics import set_metrics  # noqa: F401  (MMD-CD, COV-CD, 1-NNA-CD of two SETS of clouds)
 
 
@@ -81,10 +83,8 @@ def fused_validation_metrics(pred, gt, th=0.01, emd_eps=0.005, emd_iters=50, wit
 def _plain_search(pred, gt, pred_lengths=None, gt_lengths=None):
     """(dist1, dist2, idx1, idx2, ...) of the one Chamfer search, without autograd: the distances' bits are those of
     the differentiable call."""
-    from sparenet_amd.cuda.dcd import _check_pair, _search
-
-    _check_pair("fused_validation_metrics", pred, gt)
-    return _search(pred.detach(), gt.detach(), pred_lengths, gt_lengths)
+    _args.check_pair("fused_validation_metrics", "xyz1", pred, "xyz2", gt, same_device=True)
+    return chamfer_search_raw(pred.detach(), gt.detach(), pred_lengths, gt_lengths)
 
 
 def _consistency_from_search(pred, gt, found, k, pred_lengths=None, gt_lengths=None):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from fps_ref import fps_ref, fps_ref_batch, lattice_cloud, overflow_cloud, same_bits
+from lib_stub import install
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -143,38 +144,8 @@ def test_wrapper_refusals():
 
 @pytest.fixture()
 def stub(monkeypatch):
-    """A stub in place of the library that only CONVERTS what the call path hands it with the argtypes parsed from the
-    header (as tests/test_set_emd.py does), and records the calls."""
-    from sparenet_amd import _lib
-
-    _lib.lib()
-    calls = []
-
-    def converting(name, fn):
-        def call(*args):
-            assert len(args) == len(fn.argtypes), f"{name}: {len(args)} arguments, prototype has {len(fn.argtypes)}"
-            for i, (t, a) in enumerate(zip(fn.argtypes, args)):
-                try:
-                    t.from_param(a)
-                except (TypeError, ctypes.ArgumentError) as e:
-                    raise AssertionError(f"{name}: argument {i} ({a!r}) does not convert to {t.__name__}: {e}")
-            calls.append((name, args))
-            return 4096 if fn.restype is ctypes.c_size_t else 0
-        return call
-
-    monkeypatch.setattr(_lib, "_op_calls", {stem: {n: (converting(n, s[0]),) + s[1:] for n, s in registry.items()}
-                                            for stem, registry in _lib._op_calls.items()})
-
-    def fake_address(t, dtype, name, host=False):      # _lib._address without the device check: CPU tensors stand in
-        assert isinstance(t, torch.Tensor), name
-        assert dtype is None or t.dtype == dtype, f"{name}: expected {dtype}, got {t.dtype}"
-        assert t.is_contiguous(), name
-        return t.data_ptr() or 8
-
-    monkeypatch.setattr(_lib, "_address", fake_address)
-    monkeypatch.setattr(_lib, "require_device", lambda t, name: None)
-    monkeypatch.setattr(_lib, "stream_of", lambda t: ctypes.c_void_p(0))
-    return calls
+    """The converting, recording stub of tests/lib_stub.py in place of the library."""
+    return install(monkeypatch, ("_op_calls",))
 
 
 def _fps_args(calls):

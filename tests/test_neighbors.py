@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from lib_stub import _scalars, install
 from neighbors_ref import (ball_ref, ball_ref_batch, dist_matrix, group_backward_ref, group_ref, interpolate_ref,
                            knn_ref, knn_ref_batch, lattice_points, same_bits, sum_bound)
 
@@ -219,44 +220,8 @@ def test_wrapper_refusals():
 
 @pytest.fixture()
 def stub(monkeypatch):
-    """A stub in place of the library that only CONVERTS what the call path hands it with the argtypes parsed from the
-    header (as tests/test_fps.py does), and records the calls."""
-    from sparenet_amd import _lib
-
-    _lib.lib()
-    calls = []
-
-    def converting(name, fn):
-        def call(*args):
-            assert len(args) == len(fn.argtypes), f"{name}: {len(args)} arguments, prototype has {len(fn.argtypes)}"
-            for i, (t, a) in enumerate(zip(fn.argtypes, args)):
-                try:
-                    t.from_param(a)
-                except (TypeError, ctypes.ArgumentError) as e:
-                    raise AssertionError(f"{name}: argument {i} ({a!r}) does not convert to {t.__name__}: {e}")
-            calls.append((name, args))
-            return 4096 if fn.restype is ctypes.c_size_t else 0
-        return call
-
-    monkeypatch.setattr(_lib, "_op_calls", {stem: {n: (converting(n, s[0]),) + s[1:] for n, s in registry.items()}
-                                            for stem, registry in _lib._op_calls.items()})
-
-    def fake_address(t, dtype, name, host=False):      # _lib._address without the device check: CPU tensors stand in
-        assert isinstance(t, torch.Tensor), name
-        assert dtype is None or t.dtype == dtype, f"{name}: expected {dtype}, got {t.dtype}"
-        assert t.is_contiguous(), name
-        return t.data_ptr() or 8
-
-    monkeypatch.setattr(_lib, "_address", fake_address)
-    monkeypatch.setattr(_lib, "require_device", lambda t, name: None)
-    monkeypatch.setattr(_lib, "stream_of", lambda t: ctypes.c_void_p(0))
-    return calls
-
-
-def _scalars(args):
-    """A call's arguments without the stream, every pointer reduced to whether it was given."""
-    return tuple(a if isinstance(a, (int, float)) and not isinstance(a, bool) and abs(a) < 2 ** 20 else a is not None
-                 for a in args[:-1])
+    """The converting, recording stub of tests/lib_stub.py in place of the library."""
+    return install(monkeypatch, ("_op_calls",))
 
 
 def test_search_wrappers_pass_what_they_were_given(stub):

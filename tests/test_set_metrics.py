@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import set_metrics_ref as R
+from lib_stub import install
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXT_HEADER = os.path.join(ROOT, "include", "sparenet_hip_ext.h")
@@ -204,24 +205,9 @@ def test_wrappers_refuse_what_the_kernel_cannot_take():
 def test_wrappers_pass_convertible_arguments_and_a_set_against_itself_is_one_call(monkeypatch):
     """The call sites of the extension path, exercised as tests/test_callsites.py does for the main header: a stub in
     place of the library that only converts what ext_call hands it with the argtypes parsed from the header."""
-    from sparenet_amd import _lib
     from sparenet_amd.cuda.set_distance import chamfer_matrix
 
-    _lib.lib()
-    calls = []
-
-    def stub(name, fn):
-        def converting(*args):
-            assert len(args) == len(fn.argtypes), f"{name}: {len(args)} arguments, prototype has {len(fn.argtypes)}"
-            for t, a in zip(fn.argtypes, args):
-                t.from_param(a)
-            calls.append(name)
-            return 4096 if fn.restype is ctypes.c_size_t else 0
-        return converting
-
-    monkeypatch.setattr(_lib, "_ext_calls", {n: (stub(n, s[0]),) + s[1:] for n, s in _lib._ext_calls.items()})
-    monkeypatch.setattr(_lib, "_address", lambda t, dtype, name, host=False: t.data_ptr() or 8)
-    monkeypatch.setattr(_lib, "stream_of", lambda t: ctypes.c_void_p(0))
+    calls = install(monkeypatch, ("_ext_calls",), record=lambda name, args: name)
     x, y = torch.rand(3, 8, 3), torch.rand(2, 5, 3)
     assert chamfer_matrix(x, y).shape == (3, 2)
     assert calls.count("sn_set_chamfer_sums") == 2
