@@ -19,6 +19,7 @@ _SWD_NAMES = ("sliced_wasserstein", "sorted_projections", "random_directions", "
 _DCD_NAMES = ("density_aware_chamfer", "dcd_from_search", "DensityAwareChamferDistance")
 _NORMALS_NAMES = ("local_pca", "surface_variation", "estimate_normals", "normal_consistency", "point_to_plane_chamfer")
 _OCCUPANCY_NAMES = ("occupancy_grid",)
+_VOXEL_GRID_NAMES = ("voxel_grid", "grid_subsample", "voxel_pool", "GridPool", "VoxelGrid")
 
 
 def __getattr__(name):
@@ -44,6 +45,10 @@ def __getattr__(name):
         import importlib
 
         return getattr(importlib.import_module("sparenet_amd.cuda.occupancy"), name)
+    if name in _VOXEL_GRID_NAMES:      # voxel-grid subsampling and pooling (sparenet_amd.cuda.voxel_grid)
+        import importlib
+
+        return getattr(importlib.import_module("sparenet_amd.cuda.voxel_grid"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -67,6 +67,7 @@ __device__ __forceinline__ double record(float v, int i) {
 }
 __device__ __forceinline__ int record_index(double r) { return (int)((unsigned)__double_as_longlong(r) & (kMaxPoints - 1)); }
 
+// (voxel_grid.hip holds a copy of slot, pow2_width, sort_pass and the loop that drives it: a change here belongs there too)
 // R consecutive steps of the merge of runs of k, strides jtop, jtop / 2 ... jtop >> (R - 1), on 2^R records per lane.
 // jlow is a power of 16 (the short pass of a merge comes first), and the R bits of `a` at jlow's position are 0, so
 // slot(a + t jlow) = slot(a) + t slot(jlow): one add per record.  A run that is to come out descending is loaded in
