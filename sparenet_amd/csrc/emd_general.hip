@@ -13,6 +13,7 @@
 #include "block_scan.hpp"
 #include "common.hpp"
 #include "emd_auction.hpp"
+#include "lds_sort.hpp"
 
 namespace {
 
@@ -295,8 +296,8 @@ __global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scan_kernel(int 
 }
 
 // one workgroup per cloud: the stable scatter.  Chunk after chunk of 1024 bidders in ascending j; the chunk's
-// (target << 10 | local j) keys are sorted (bitonic, in LDS), a bidder's rank among the chunk's bidders of its target is
-// its distance from the first key of the target, and the last of them advances the target's run.
+// (target << 10 | local j) keys are sorted (lds_sort.hpp's key sort), a bidder's rank among the chunk's bidders of its
+// target is its distance from the first key of the target, and the last of them advances the target's run.
 template <bool kRagged>
 __global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scatter_kernel(int n, int m,
                                                                                const int *__restrict__ assignment,
@@ -311,18 +312,7 @@ __global__ __launch_bounds__(kSortThreads) void emd_general_bwd_scatter_kernel(i
     const int k = j >= n ? -1 : kRagged ? held_target<kRagged>(assignment, c, j, n, m, r) : assignment[c * n + j];
     sk[tid] = (k >= 0 && k < m) ? ((unsigned)k << 10) | (unsigned)tid : kNone;  // k < 2^20: fits
     __syncthreads();
-    for (int size = 2; size <= kSortThreads; size <<= 1)
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        const int partner = tid ^ stride;
-        if (partner > tid) {
-          const unsigned x = sk[tid], y = sk[partner];
-          if ((x > y) == ((tid & size) == 0)) {
-            sk[tid] = y;
-            sk[partner] = x;
-          }
-        }
-        __syncthreads();
-      }
+    lds_sort::sort_keys<kSortThreads>(sk, kSortThreads);
     const unsigned key = sk[tid];
     int rank = 0, tk = 0;
     if (key != kNone) {

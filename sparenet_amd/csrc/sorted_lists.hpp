@@ -7,6 +7,7 @@
 // follows the sort differs between them (fp32 by one wave, double by the workgroup) and stays in their kernels.
 #pragma once
 #include "common.hpp"
+#include "lds_sort.hpp"
 
 namespace {
 
@@ -55,9 +56,9 @@ __device__ __forceinline__ void sort_ints(int *a, int n) {
 }
 
 // A workgroup of kThreads sorts the c entries of lst; keys is its LDS buffer of kLongSortCap ints.  Up to kLongSortCap
-// entries: padded to a power of two with 0x7fffffff, bitonic network in keys, lst untouched.  Beyond: thread 0 sorts
-// lst in place.  Opens with a barrier (the previous list's keys are no longer needed) and closes with one: afterwards
-// every thread reads entry i through sorted_entry.
+// entries: padded to a power of two with 0x7fffffff, lds_sort.hpp's key sort in keys, lst untouched.  Beyond: thread 0
+// sorts lst in place.  Opens with a barrier (the previous list's keys are no longer needed) and closes with one:
+// afterwards every thread reads entry i through sorted_entry.
 template <int kThreads>
 __device__ __forceinline__ void sort_long_list(int *lst, int c, int *keys) {
   const int tid = threadIdx.x;
@@ -67,21 +68,7 @@ __device__ __forceinline__ void sort_long_list(int *lst, int c, int *keys) {
     while (p2 < c) p2 <<= 1;
     for (int i = tid; i < p2; i += kThreads) keys[i] = i < c ? lst[i] : 0x7fffffff;
     __syncthreads();
-    for (int k = 2; k <= p2; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < p2; i += kThreads) {
-          const int ixj = i ^ j;
-          if (ixj > i) {
-            const int x = keys[i], y = keys[ixj];
-            const bool up = (i & k) == 0;
-            if ((x > y) == up) {
-              keys[i] = y;
-              keys[ixj] = x;
-            }
-          }
-        }
-        __syncthreads();
-      }
+    lds_sort::sort_keys<kThreads>(keys, p2);
   } else {
     if (tid == 0) sort_ints(lst, c);
     __threadfence_block();

@@ -8,14 +8,8 @@
 //       records are equal.  -0.0 is made +0.0 before the key is taken (the two compare equal); the array is padded to a
 //       power of two W with records 2.0, which sort behind every point, +inf included.  A cloud of 16384 points is
 //       128 KiB of records: the sort never leaves LDS.
-//       The network's log2(W) (log2(W) + 1) / 2 compare-exchange steps are taken up to four at a time: a lane loads the
-//       16 records a + t * jlow (t = 0..15) that four consecutive steps of strides 8 jlow .. jlow couple among
-//       themselves, runs the four steps in registers and stores them -- 32 passes over LDS instead of 105 at W = 16384,
-//       one barrier each.  Where a merge has a number of steps that is no multiple of four the short pass comes first,
-//       at the wide strides, so a pass's lowest stride jlow is a power of 16.  Slot i lives at record i + i / 16: without the gap the last pass of a merge (jlow = 1, a
-//       lane owns 16 consecutive records = 128 bytes) puts every lane of a group on the same two bank quarters; with it
-//       a lane's stride is 34 dwords and the 32 lanes of a ds_read_b64 group fall on 32 different bank pairs.  The
-//       passes with jlow >= 32 read consecutive records across lanes and meet a gap once per 16 lanes.
+//       lds_sort.hpp is the network (four steps per pass over LDS in registers, one empty record behind every 16) and
+//       says why such records make a compare-exchange one v_min_f64 and one v_max_f64.
 //       LDS: (16384 + 1024) * 8 = 139264 bytes, all dynamic (the base stays 16-byte aligned), one workgroup per CU.
 //   swd_transport_kernel      one workgroup per (cloud, slice, side), one sorted rank per lane and step: the rank finds
 //       its partners on the other side from the mass intervals alone -- no serial merge -- adds its terms in double and
@@ -24,33 +18,22 @@
 //   swd_accumulate_kernel     one lane per point: adds the chunk's coefficient * direction to the gradient in slice
 //       order, from 0 in the first chunk, times 1 / L in the last.
 #include "common.hpp"
+#include "lds_sort.hpp"
 #include "../../include/ops/swd.h"
 
 namespace {
 
 using u64 = unsigned long long;
+using namespace lds_sort;      // kThreads, slot, lds_bytes, pow2_width, sort_records
 
 constexpr int kMaxPoints = 16384;          // a cloud's records fit one workgroup's LDS
-constexpr int kThreads = 1024;
-constexpr int kPadShift = 4;               // one empty record behind every 16
-constexpr int kStepsPerPass = 4;           // compare-exchange steps a lane runs in registers between two barriers
 constexpr int kChunkWorkgroups = 512;      // default chunk: this many (cloud, slice) pairs per launch
 constexpr int kAccThreads = 256;
 constexpr int kIndexBits = 14;             // a record's index field
 constexpr u64 kRecordOne = 0x3ff0000000000000ull, kRecordPad = 0x4000000000000000ull;      // 1.0; 2.0 sorts behind all
 
-__host__ __device__ constexpr int slot(int i) { return i + (i >> kPadShift); }
-constexpr size_t lds_bytes(int width) { return (size_t)slot(width) * sizeof(double); }
-
 static_assert(kMaxPoints == 1 << kIndexBits, "the sort's width is a power of two and an index fits its field");
 static_assert(lds_bytes(kMaxPoints) == 139264 && lds_bytes(kMaxPoints) <= 160 * 1024, "LDS of one gfx950 CU");
-static_assert(kStepsPerPass == kPadShift, "a pass's lowest stride is a power of 16: whole padded rows, or 1");
-
-__host__ __device__ inline int pow2_width(int len) {      // the smallest power of two >= max(len, 2)
-  int w = 2;
-  while (w < len) w <<= 1;
-  return w;
-}
 
 __device__ __forceinline__ float project(const float *pts, int i, float tx, float ty, float tz) {
   const float *q = pts + (size_t)i * 3;
@@ -66,38 +49,6 @@ __device__ __forceinline__ double record(float v, int i) {
   return __longlong_as_double((long long)(kRecordOne | ((u64)sn::ordered_key(c) << kIndexBits) | (unsigned)i));
 }
 __device__ __forceinline__ int record_index(double r) { return (int)((unsigned)__double_as_longlong(r) & (kMaxPoints - 1)); }
-
-// (voxel_grid.hip holds a copy of slot, pow2_width, sort_pass and the loop that drives it: a change here belongs there too)
-// R consecutive steps of the merge of runs of k, strides jtop, jtop / 2 ... jtop >> (R - 1), on 2^R records per lane.
-// jlow is a power of 16 (the short pass of a merge comes first), and the R bits of `a` at jlow's position are 0, so
-// slot(a + t jlow) = slot(a) + t slot(jlow): one add per record.  A run that is to come out descending is loaded in
-// reverse -- register t holds record E - 1 - t -- so the network in the registers is the ascending one for every lane.
-template <int R>
-__device__ __forceinline__ void sort_pass(double *rec, int width, int k, int jtop, int tid) {
-  constexpr int E = 1 << R;
-  const int jlow = jtop >> (R - 1);
-  const int stride = slot(jlow);
-  for (int q = tid; q < (width >> R); q += kThreads) {
-    const int a = ((q & ~(jlow - 1)) << R) | (q & (jlow - 1));      // R zero bits at jlow's position
-    const bool up = (a & k) == 0;      // k >= 2 * jtop: the same for all E records
-    const int base = slot(a) + (up ? 0 : (E - 1) * stride), step = up ? stride : -stride;
-    double e[E];
-#pragma unroll
-    for (int t = 0; t < E; ++t) e[t] = rec[base + t * step];
-#pragma unroll
-    for (int d = E >> 1; d >= 1; d >>= 1) {
-#pragma unroll
-      for (int t = 0; t < E; ++t) {
-        if (t & d) continue;
-        const double lo = __builtin_fmin(e[t], e[t | d]), hi = __builtin_fmax(e[t], e[t | d]);
-        e[t] = lo;
-        e[t | d] = hi;
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < E; ++t) rec[base + t * step] = e[t];
-  }
-}
 
 struct SortSide {
   const float *pts;       // [b, n, 3]
@@ -129,23 +80,7 @@ __global__ __launch_bounds__(kThreads) void swd_project_sort_kernel(SortArgs a) 
     rec[slot(i)] = i < len ? record(project(pts, i, tx, ty, tz), i) : __longlong_as_double((long long)kRecordPad);
   }
   __syncthreads();
-  if (len > 1) {      // uniform over the workgroup
-    for (int k = 2, steps = 1; k <= width; k <<= 1, ++steps) {
-      int jtop = k >> 1;
-      for (int left = steps; left > 0;) {
-        const int r = left % kStepsPerPass ? left % kStepsPerPass : kStepsPerPass;
-        switch (r) {
-          case 1: sort_pass<1>(rec, width, k, jtop, tid); break;
-          case 2: sort_pass<2>(rec, width, k, jtop, tid); break;
-          case 3: sort_pass<3>(rec, width, k, jtop, tid); break;
-          default: sort_pass<4>(rec, width, k, jtop, tid); break;
-        }
-        __syncthreads();
-        jtop >>= r;
-        left -= r;
-      }
-    }
-  }
+  if (len > 1) sort_records(rec, width, tid);      // uniform over the workgroup
   const size_t row = ((size_t)b * a.stride + lc) * s.n;
   for (int r = tid; r < s.n; r += kThreads) {
     const int i = r < len ? record_index(rec[slot(r)]) : -1;

@@ -4,9 +4,8 @@
 //   voxel_resident_kernel   n <= 16384.  One workgroup of 1024 lanes owns whole clouds and loops over them.  A point
 //       becomes the 64-bit record ((key << 14) | index) + 2^52 in LDS: below 2^62 + 2^52 and at least 2^52, so as a double
 //       it is positive, finite and NORMAL (without the 2^52 the cells next to -32768 would be denormals) and two records
-//       compare as their bit patterns do -- a compare-exchange is one v_min_f64 and one v_max_f64, as in swd.hip, whose
-//       bitonic network (four steps per pass over LDS, one empty record behind every
-//       16) this file repeats in its own copy (swd.hip names the twin).  Padding rows and points in no voxel get the
+//       compare as their bit patterns do -- a compare-exchange is one v_min_f64 and one v_max_f64: the records
+//       are sorted by lds_sort.hpp's network, as those of swd.hip are.  Padding rows and points in no voxel get the
 //       record 4.0, which sorts behind every point.  Behind the sort reduce_cloud() runs on the LDS records.
 //   voxel_chunk_sort_kernel, voxel_merge_kernel, voxel_reduce_kernel   n above the resident size.  Chunks of the
 //       resident size are sorted the same way (the record's index is the position inside the chunk) and written to the
@@ -26,86 +25,27 @@
 #include "block_scan.hpp"
 #include "common.hpp"
 #include "host_threads.hpp"
+#include "lds_sort.hpp"
 #include "voxel_cell.hpp"
 #include "../../include/ops/voxel_grid.h"
 
 namespace {
 
+using namespace lds_sort;      // kThreads, slot, lds_bytes, pow2_width, sort_records
 using voxel_cell::kNoKey;
 using voxel_cell::u64;
 
 constexpr int kResidentMax = 16384;        // a cloud's records fit one workgroup's LDS
 constexpr int kBigMax = 1 << 24;           // the workspace path's limit
-constexpr int kThreads = 1024;
-constexpr int kPadShift = 4;               // one empty record behind every 16
-constexpr int kStepsPerPass = 4;           // compare-exchange steps a lane runs in registers between two barriers
 constexpr int kIndexBits = 14;             // a record's index field
 constexpr int kMergeThreads = 256, kPoolThreads = 256;
 constexpr u64 kRecordBias = 1ull << 52;                  // added to every record: the exponent field is never 0
 constexpr u64 kRecordPad = (kNoKey << kIndexBits) + kRecordBias;      // behind every record; its key field is kNoKey
 
-__host__ __device__ constexpr int slot(int i) { return i + (i >> kPadShift); }
-constexpr size_t lds_bytes(int width) { return (size_t)slot(width) * sizeof(double); }
-
 static_assert(kResidentMax == 1 << kIndexBits, "the sort's width is a power of two and an index fits its field");
 static_assert(lds_bytes(kResidentMax) == 139264 && lds_bytes(kResidentMax) + 256 <= 160 * 1024, "LDS of one gfx950 CU");
-static_assert(kStepsPerPass == kPadShift, "a pass's lowest stride is a power of 16: whole padded rows, or 1");
 static_assert(((kRecordPad - kRecordBias) >> kIndexBits) == kNoKey, "the pad record's key is that of a point in no voxel");
 static_assert(kRecordPad == 0x4010000000000000ull, "4.0: a normal, finite double, as every record below it");
-
-__host__ __device__ inline int pow2_width(int len) {      // the smallest power of two >= max(len, 2)
-  int w = 2;
-  while (w < len) w <<= 1;
-  return w;
-}
-
-// R consecutive steps of the merge of runs of k (swd.hip: sort_pass)
-template <int R>
-__device__ __forceinline__ void sort_pass(double *rec, int width, int k, int jtop, int tid) {
-  constexpr int E = 1 << R;
-  const int jlow = jtop >> (R - 1);
-  const int stride = slot(jlow);
-  for (int q = tid; q < (width >> R); q += kThreads) {
-    const int a = ((q & ~(jlow - 1)) << R) | (q & (jlow - 1));      // R zero bits at jlow's position
-    const bool up = (a & k) == 0;      // k >= 2 * jtop: the same for all E records
-    const int base = slot(a) + (up ? 0 : (E - 1) * stride), step = up ? stride : -stride;
-    double e[E];
-#pragma unroll
-    for (int t = 0; t < E; ++t) e[t] = rec[base + t * step];
-#pragma unroll
-    for (int d = E >> 1; d >= 1; d >>= 1) {
-#pragma unroll
-      for (int t = 0; t < E; ++t) {
-        if (t & d) continue;
-        const double lo = __builtin_fmin(e[t], e[t | d]), hi = __builtin_fmax(e[t], e[t | d]);
-        e[t] = lo;
-        e[t | d] = hi;
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < E; ++t) rec[base + t * step] = e[t];
-  }
-}
-
-// the records rec[slot(0 .. width - 1)] ascending; every lane of the workgroup calls it, the records are written and a
-// barrier has been passed.  Ends in a barrier.
-__device__ __forceinline__ void sort_records(double *rec, int width, int tid) {
-  for (int k = 2, steps = 1; k <= width; k <<= 1, ++steps) {
-    int jtop = k >> 1;
-    for (int left = steps; left > 0;) {
-      const int r = left % kStepsPerPass ? left % kStepsPerPass : kStepsPerPass;
-      switch (r) {
-        case 1: sort_pass<1>(rec, width, k, jtop, tid); break;
-        case 2: sort_pass<2>(rec, width, k, jtop, tid); break;
-        case 3: sort_pass<3>(rec, width, k, jtop, tid); break;
-        default: sort_pass<4>(rec, width, k, jtop, tid); break;
-      }
-      __syncthreads();
-      jtop >>= r;
-      left -= r;
-    }
-  }
-}
 
 struct GridArgs {
   const float *xyz;        // [b, n, 3]
