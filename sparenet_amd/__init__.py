@@ -20,6 +20,7 @@ _DCD_NAMES = ("density_aware_chamfer", "dcd_from_search", "DensityAwareChamferDi
 _NORMALS_NAMES = ("local_pca", "surface_variation", "estimate_normals", "normal_consistency", "point_to_plane_chamfer")
 _OCCUPANCY_NAMES = ("occupancy_grid",)
 _VOXEL_GRID_NAMES = ("voxel_grid", "grid_subsample", "voxel_pool", "GridPool", "VoxelGrid")
+_REGISTRATION_NAMES = ("transform_points", "rigid_fit", "icp", "aligned_chamfer", "RigidFit", "IcpResult")
 
 
 def __getattr__(name):
@@ -49,6 +50,10 @@ def __getattr__(name):
         import importlib
 
         return getattr(importlib.import_module("sparenet_amd.cuda.voxel_grid"), name)
+    if name in _REGISTRATION_NAMES:      # rigid registration: Kabsch fit and ICP (sparenet_amd.cuda.registration)
+        import importlib
+
+        return getattr(importlib.import_module("sparenet_amd.cuda.registration"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -44,6 +44,27 @@ __device__ __forceinline__ double block_sum_f64(double acc, double *wave_sum) {
   return acc;
 }
 
+// block_sum_f64 for kValues values per thread at once, each in block_sum_f64's order: wave_sums is kThreads / kWave *
+// kValues doubles of LDS, and thread k < kValues returns the sum of value k in acc[0] (the other threads' acc is
+// spent).  One barrier inside; the caller leaves wave_sums alone until those threads have passed a later barrier.
+template <int kThreads, int kValues>
+__device__ __forceinline__ void block_sums_f64(double (&acc)[kValues], double *wave_sums) {
+  static_assert(kThreads % kWave == 0 && kValues <= kThreads, "whole waves, one summing thread per value");
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kValues; ++k) {
+    double v = acc[k];
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((tid & (kWave - 1)) == 0) wave_sums[(tid / kWave) * kValues + k] = v;
+  }
+  __syncthreads();
+  if (tid < kValues) {
+    double v = wave_sums[tid];
+    for (int w = 1; w < kThreads / kWave; ++w) v += wave_sums[w * kValues + tid];
+    acc[0] = v;
+  }
+}
+
 // Lives in __shared__ memory of a one-dimensional workgroup of kThreads threads; all of them call reset and chunk.
 // The alignment belongs to the variable, not to the type: an aligned type would round these 68 bytes up to 80.
 template <int kThreads>

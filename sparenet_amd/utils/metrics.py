@@ -174,6 +174,15 @@ def normal_consistency(pred, gt, k=16, pred_lengths=None, gt_lengths=None, pred_
     return consistency(pred, gt, pred_normals, gt_normals, k, pred_lengths, gt_lengths)
 
 
+def aligned_chamfer(pred, gt, **icp_options):
+    """Chamfer distance of pred [B,N,3] and gt [B,M,3] per sample [B] after pred has been registered onto gt by ICP
+    (sparenet_amd.cuda.registration.aligned_chamfer, whose options these are: iters, mode, max_dist, init, ...): the
+    pose-free distance for scans that do not share the prediction's frame.  mean dist1 + mean dist2, not scaled."""
+    from sparenet_amd.cuda.registration import aligned_chamfer as aligned
+
+    return aligned(pred, gt, **icp_options)[0]
+
+
 def jsd(pred, gt, resolution=28, in_sphere=True, pred_lengths=None, gt_lengths=None, gt_counts=None):
     """Jensen-Shannon divergence (bits, float64 scalar in [0, 1]) between the occupancy distributions of the SETS pred
     [N,n,3] and gt [M,m,3] on the resolution^3 grid clipped to the unit sphere
